@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- W8A8 linear hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path (activation quantise -> INT8 MFMA GEMM -> fused
@@ -370,6 +370,40 @@ def run_step(mods, spec, xs):
         ms = [mods[l] for l in labels]
         outs.update(zip(labels, concurrent_linears(ms, shared_input(xs[key], *ms))))
     return [outs[label] for label, kind, K, N, aq, bias in spec]
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: .npy payload of all arrays together (under 64 MB with room for the headers)
+
+
+def output_sample(result, labels, seed=0):
+    """--dump-outputs: what one step returned, as {name: float32 [rows, last dim] on the device}.  A list of outputs is named by the step's linear
+    labels, a single tensor "out".  When the outputs together exceed DUMP_BYTES each keeps an equal share of it: the same fixed, seeded
+    (numpy RandomState(seed)), sorted subset of its rows, so two runs with the same arguments write the same rows."""
+    import numpy as np
+    outs = {"out": result} if isinstance(result, torch.Tensor) else dict(zip(labels, result, strict=True))
+    share = DUMP_BYTES // len(outs)
+    sample = {}
+    for name, t in outs.items():
+        rows = t.detach().reshape(-1, t.shape[-1])
+        n, width = rows.shape
+        keep = min(n, max(1, share // (4 * width)))
+        if keep < n:
+            idx = np.sort(np.random.RandomState(seed).choice(n, keep, replace=False))
+            rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        sample[name] = (rows.float(), list(t.shape))
+    return sample
+
+
+def write_outputs(sample, dirpath):
+    """Write output_sample()'s arrays as DIR/<name>.npy; returns what the JSON line reports about them."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {}
+    for name, (rows, shape) in sample.items():
+        np.save(os.path.join(dirpath, name + ".npy"), rows.cpu().numpy())
+        arrays[name] = {"shape": shape, "rows_written": rows.shape[0]}
+    return {"dir": dirpath, "dtype": "float32", "arrays": arrays,
+            "sample": f"rows of the last timed step's outputs; a numpy RandomState(0) row subset when all would exceed {DUMP_BYTES} bytes"}
 
 
 def measure_dominant_kernel(mod, x, iters=20, batch=50, warm=200, plain_compare=True, warm_ms=0.0):
@@ -1008,8 +1042,13 @@ def main():
     ap.add_argument("--no-plain-compare", action="store_true", help="skip the plain-operand timing of the dominant kernel (rocprofv3 passes: the comparison launches carry the same kernel name as the offset-image launches and would mix into its average)")
     ap.add_argument("--no-other-configs", action="store_true", help="default workload only: skip the short cfg2 / cfg4 / cfg5 measurements (block 'configs')")
     ap.add_argument("--no-cfg3", action="store_true", help="default workload only: skip the LLaMA-2-7B 32-layer decoder forward (BASELINE configs[2]) that is timed after the main step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32; a fixed seeded row sample when larger than "
+                         f"{DUMP_BYTES >> 20} MiB in all): the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)   # internal: one pinned leg of cpu_baseline() in its own process
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_leg:
         cpu_leg(*json.loads(args.cpu_leg))
         return
@@ -1173,14 +1212,18 @@ def main():
         step()
     sync_all()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()   # (kept for --dump-outputs)
     sync_all()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # (the graph's replay returns nothing: its outputs live in the buffers the capture returned)
+    dump = output_sample(graph_out if args.graph else last, [s[0] for s in spec]) if (args.dump_outputs and rank == 0) else None
+    del last
 
     # the same step with q / k / v as ONE GEMM over the three modules' stacked int8 rows (the reference's own W8A8BFP32OFP32QKVLinear class,
     # harness.qkv_from_parts: bit-identical outputs, two launch-to-launch gaps fewer).  Reported beside the main value, never instead of it.
@@ -1352,6 +1395,8 @@ def main():
             out["config"]["norm"] = "fused RMSNorm->int8 (N1)" if args.fuse_norm else "torch RMSNorm (weight/input_scale) + per-linear quantise"
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(spec, min(M, 4096), args.dtype, mods=None if (layer_mode or moe_mode) else mods, xs=None if (layer_mode or moe_mode) else xs)
+        if dump is not None:
+            out["dump_outputs"] = write_outputs(dump, args.dump_outputs)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

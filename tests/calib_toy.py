@@ -5,6 +5,12 @@ import torch
 
 import detrng
 
+# The collectors see the outputs of a float32 forward on the host, whose last bits follow the kernels MKL and ATen pick for the host's instruction
+# set (and, for MKL, its thread count).  The fixture is recorded, and compared exactly, under this environment, which selects the same code paths
+# on every x86-64 host: MKL's conditional numerical reproducibility in its "COMPATIBLE" mode, ATen's generic kernels, one thread.  It must be in
+# force before torch runs its first operation, i.e. in the environment of a fresh interpreter.
+PINNED_NUMERICS = {"MKL_CBWR": "COMPATIBLE", "ATEN_CPU_CAPABILITY": "default", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+
 
 def _det_init(model, seed, std=0.08):
     with torch.no_grad():

@@ -8,7 +8,8 @@ The module imports `autosmoothquant.models._MODEL_TYPE`; autosmoothquant/models/
   tests/golden/calib_dataset.jsonl     the dataset the reference's load_dataset("json", ...) reads
   tests/golden/g9_calib.npz            per model: the token ids in the order the reference fed them (after its shuffle(seed=42)),
                                        act_scales (per-channel absmax per nn.Linear), act_dict (per-tensor in/out absmax), decoder_layer_scales
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_calib.py
+The forward runs under tests/calib_toy.py's PINNED_NUMERICS (the same code paths on every x86-64 host), which the tests use for the exact comparison.
+Usage:  MKL_CBWR=COMPATIBLE ATEN_CPU_CAPABILITY=default OMP_NUM_THREADS=1 MKL_NUM_THREADS=1 PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_calib.py
 """
 import json
 import os
@@ -47,6 +48,9 @@ import calib_toy  # noqa: E402
 
 
 def main():
+    unpinned = {k: v for k, v in calib_toy.PINNED_NUMERICS.items() if os.environ.get(k) != v}
+    if unpinned:
+        raise SystemExit(f"run under calib_toy.PINNED_NUMERICS: missing {unpinned}")
     ds_path = os.path.join(HERE, "calib_dataset.jsonl")
     with open(ds_path, "w") as f:
         for t in calib_toy.DATASET:
@@ -78,5 +82,5 @@ def main():
 
 if __name__ == "__main__":
     torch.manual_seed(0)
-    torch.set_num_threads(8)
+    torch.set_num_threads(1)
     main()

@@ -134,7 +134,16 @@ def check_against_reference_fixture(tag, device="cpu", rtol=0.0):
 
 @pytest.mark.parametrize("tag", ["llama", "opt"])
 def test_collectors_equal_the_reference_collectors(tag):
-    check_against_reference_fixture(tag)      # same torch CPU kernels on the same inputs: exact
+    """Same torch CPU kernels on the same inputs: exact.  The kernels are the ones calib_toy.PINNED_NUMERICS selects (the fixture was recorded under
+    it), so the comparison runs in a fresh interpreter started with that environment; without it the last bits follow the host's CPU."""
+    import subprocess
+    import sys
+    import calib_toy
+    tests = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]\nimport test_calibration_cpu as t\nt.check_against_reference_fixture(%r)" % (os.path.dirname(tests), tests, tag)
+    env = dict(os.environ, **calib_toy.PINNED_NUMERICS, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    r = subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
 
 
 def test_reference_dataset_fixture_matches_the_toy_corpus():
