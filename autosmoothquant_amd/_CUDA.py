@@ -1,6 +1,8 @@
 """Drop-in for the reference's native module ``autosmoothquant._CUDA`` (pybind11 class
 ``I8CUGEMM``, csrc/int8gemm/bindings.cpp:145-155): same class name, ctor and the five
-method names / argument orders, implemented over libasq_hip.so.
+method names / argument orders, implemented over libasq_hip.so -- plus the batched int8
+matmuls of csrc/kernels/bindings.cpp:16-19 (``bmm_s8t_s8n_s8t / _f32t / _s32t``) as
+module-level functions with the reference's names and argument orders.
 
 Differences that are deliberate:
   * stateless: no cuBLASLt handle, no process-wide mutex, and the CURRENT torch stream is
@@ -39,3 +41,19 @@ class I8CUGEMM:
         out = bias.view(1, -1).repeat(input.shape[0], 1)
         ops.gemm_i8_i8(input, weight, out, alpha, beta)
         return out
+
+
+# Batched int8 matmuls (csrc/kernels/bmm.cu:10-211): A int8 [B, M, K], B int8 [B, N, K] -> a new [B, M, N] tensor = A[b] . B[b]^T
+def bmm_s8t_s8n_s8t(A, B, alpha):
+    """int8 out = sat_i8(rne(alpha * float(acc)))  (CUTLASS LinearCombinationClamp, beta = 0)."""
+    return ops.bmm_i8(A, B, torch.int8, alpha)
+
+
+def bmm_s8t_s8n_f32t(A, B, alpha):
+    """float out = alpha * float(acc)  (CUTLASS LinearCombination, beta = 0)."""
+    return ops.bmm_i8(A, B, torch.float32, alpha)
+
+
+def bmm_s8t_s8n_s32t(A, B):
+    """int32 out = acc (exact)."""
+    return ops.bmm_i8(A, B, torch.int32)

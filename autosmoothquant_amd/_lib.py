@@ -11,6 +11,7 @@ ASQ_ACT_ROUND, ASQ_ACT_DIV, ASQ_ACT_PER_TOKEN = 0, 1, 2
 ASQ_EPI_SCALE_FIRST, ASQ_EPI_ACC_FIRST = 0, 1
 ASQ_SILU_FAST = 2   # bit 1 of asq_silu_mul_quantize's per_token / asq_linear_w8a8_gate_up's flags
 ASQ_FP8_PER_TOKEN, ASQ_FP8_PER_TENSOR, ASQ_FP8_STATIC = 0, 1, 2
+ASQ_BMM_S32, ASQ_BMM_F32, ASQ_BMM_S8 = 0, 1, 2   # asq_bmm_i8 out_kind: int32 acc, alpha * float(acc), sat_i8(rne(alpha * float(acc)))
 
 ASQ_VERSION = 126   # include/asq_hip.h: the C-ABI this loader was written against
 _lock = threading.Lock()
@@ -67,6 +68,8 @@ SIGNATURES = {
     "asq_cast_e5m2": (_int, [_vp, _int, _vp, _i64, _vp]),
     "asq_quantize_mxfp8": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _vp]),
     "asq_linear_mxfp8": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp]),
+    "asq_bmm_i8": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _f32, _vp]),
+    "asq_bmm_kernel_name": (ctypes.c_char_p, [_i64, _i64, _i64, _i64, _int]),
 }
 
 

@@ -1,0 +1,289 @@
+// Batched int8 A . B^T with three epilogues: the reference's bmm_s8t_s8n_{s32t,f32t,s8t} (csrc/kernels/bmm.cu:10-211, bindings.cpp:16-19),
+// CUTLASS GemmBatched over [B, M, K] x [B, N, K] -> [B, M, N] with LinearCombination (f32) / LinearCombinationClamp (int8), beta = 0.
+//
+//   acc[b, m, n] = sum_k a[b, m, k] * b[b, n, k]                      exact int32, two's-complement wrap-around (as asq_gemm_i8_i32)
+//   ASQ_BMM_S32: out = acc
+//   ASQ_BMM_F32: out = alpha * float(acc)                             EpiDequant<ASQ_F32>::one with the scalar scale: one fp32 product
+//   ASQ_BMM_S8 : out = sat_i8(rne(alpha * float(acc)))                EpiI8::one with beta = 0 (asq_gemm_i8_i8)
+//
+// Two kernels, both on v_mfma_i32_16x16x64_i8 (MmaI8x16), both over ONE 1-D grid of (batch, M tile, N tile), batch-major with the N tile fastest and
+// XCD-remapped, so neighbouring workgroups of one XCD share a batch's panels in its L2; a grid-stride loop covers any tile count:
+//   bmm_i8_t128  128 x 128 output tiles, 4 waves of 64 x 64, K in steps of 128 through a 32 KiB LDS tile with one K step prefetched in registers.
+//                The epilogue is what bounds the prefill shapes (QK^T: 537 MB of f32 out against 34 GOP): finished values go through the same LDS
+//                as a [64 rows][128 outputs] image (16-B chunks XOR-swizzled by the row) and leave as whole row segments -- 512 B per f32 / int32
+//                row, 128 B per int8 row, two rows per wave store instruction for 4-byte outputs, eight for int8.
+//   bmm_i8_m16   M <= 16 (decode): one 16-row MFMA tile, 32 output columns per block; each wave streams its share of the K steps of B straight into
+//                MFMA fragments with 16-B loads (no LDS for the operands, no 128-row padding), the four waves' partial sums meet in LDS.
+// Loads: unguarded 16-B loads when K % 16 == 0 and the operands are 16-B aligned, otherwise load16_guarded's zero-filled byte path (any K, any
+// alignment).  Every offset is 64-bit.  No workspace, no split-K across workgroups.
+#include "asq_gemm_kernels.h"
+
+namespace asq {
+
+// The output encodings: 4 accumulators of one lane (4 consecutive columns of one row) -> stored bits, arithmetic of the 2-D epilogues.
+template <int KIND> struct BmmOut;
+template <> struct BmmOut<ASQ_BMM_S32> {
+    static constexpr int kBytes = 4;
+    __device__ static __forceinline__ uint32_t one(int acc, float) { return (uint32_t)acc; }
+};
+template <> struct BmmOut<ASQ_BMM_F32> {
+    static constexpr int kBytes = 4;
+    __device__ static __forceinline__ uint32_t one(int acc, float alpha)
+    {
+        const EpiDequant<ASQ_F32, false, false, false> e{nullptr, 0, nullptr, nullptr, nullptr, nullptr, alpha, ASQ_EPI_SCALE_FIRST, false};
+        return __float_as_uint(e.one(acc, alpha, 1.0f, 0.0f));
+    }
+};
+template <> struct BmmOut<ASQ_BMM_S8> {
+    static constexpr int kBytes = 1;
+    __device__ static __forceinline__ uint32_t one(int acc, float alpha)
+    {
+        const EpiI8 e{nullptr, 0, alpha, 0.0f, false};
+        return (uint32_t)e.one(acc, 0) & 0xFF;
+    }
+};
+
+// 4-byte outputs: the 4 values as a 16-B chunk; int8: packed into one dword (byte i = column n + i)
+template <int KIND> __device__ __forceinline__ v4i bmm_pack16(const v4i &acc, float alpha)
+{
+    using O = BmmOut<KIND>;
+    return (v4i){(int)O::one(acc[0], alpha), (int)O::one(acc[1], alpha), (int)O::one(acc[2], alpha), (int)O::one(acc[3], alpha)};
+}
+template <int KIND> __device__ __forceinline__ uint32_t bmm_pack4(const v4i &acc, float alpha)
+{
+    using O = BmmOut<KIND>;
+    return O::one(acc[0], alpha) | (O::one(acc[1], alpha) << 8) | (O::one(acc[2], alpha) << 16) | (O::one(acc[3], alpha) << 24);
+}
+
+// Store min(rem, 16 / EB) finished elements of one row, the first at element offset `off`: whole when `vec` (16-B aligned) and all of them are in range.
+template <int EB> __device__ __forceinline__ void bmm_store_chunk(void *out, int64_t off, const v4i &v, int64_t rem, bool vec)
+{
+    constexpr int PER = 16 / EB;
+    char *p = (char *)out + off * EB;
+    if (vec && rem >= PER) {
+        *(v4i *)p = v;
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+        if (e >= rem) break;
+        if constexpr (EB == 4) ((int32_t *)p)[e] = v[e];
+        else p[e] = (char)((uint32_t)v[e >> 2] >> (8 * (e & 3)));
+    }
+}
+
+constexpr int BMM_TM = 128, BMM_TN = 128, BMM_TK = 128;
+
+template <int KIND>
+__global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 ? 3 : 2) bmm_i8_t128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
+                                                   int64_t K, int64_t tiles_m, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec)
+{
+    constexpr int EB = BmmOut<KIND>::kBytes, RB = BMM_TN * EB, NC = RB / 16;   // staging image: 64 rows of RB bytes = NC 16-B chunks
+    static_assert(64 * RB <= 2 * BMM_TM * BMM_TK, "the staging image reuses the operand tiles");
+    __shared__ __attribute__((aligned(16))) char lds[2 * BMM_TM * BMM_TK];   // [A tile 128 x 128 B | B tile 128 x 128 B], later the staging image
+    char *const xs = lds, *const ws = lds + BMM_TM * BMM_TK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int t16 = lane & 15, q16 = lane >> 4;
+    const int64_t per_batch = tiles_m * tiles_n, nsteps = (K + BMM_TK - 1) / BMM_TK;
+
+    for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
+        const int64_t bt = id / per_batch, r = id - bt * per_batch;
+        const int64_t m0 = (r / tiles_n) * BMM_TM, n0 = (r % tiles_n) * BMM_TN;
+        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
+
+        // K step = [128 rows][128 B] of each operand; thread tid moves chunks tid + 256 i (row = chunk >> 3, 16-B column = chunk & 7).
+        // LDS chunk index ^= (row >> 1) & 7: conflict-free fragment reads (the image of gemm_i8_p4x16).
+        v4i px[4], pw[4];
+        auto load = [&](int64_t k0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = tid + 256 * i, row = c >> 3, ch = c & 7;
+                px[i] = load16_guarded(ab, K, m0 + row, M, k0 + ch * 16, K, fast);
+                pw[i] = load16_guarded(bb, K, n0 + row, N, k0 + ch * 16, K, fast);
+            }
+        };
+        v4i acc[4][4];   // [m tile][n tile] of the wave's 64 x 64
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = (v4i){0, 0, 0, 0};
+        if (nsteps > 0) load(0);
+        for (int64_t s = 0; s < nsteps; ++s) {
+            __syncthreads();   // the previous step's fragments have been read
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = tid + 256 * i, row = c >> 3, ch = c & 7;
+                const int off = row * BMM_TK + ((ch ^ ((row >> 1) & 7)) << 4);
+                *(v4i *)(xs + off) = px[i];
+                *(v4i *)(ws + off) = pw[i];
+            }
+            __syncthreads();
+            if (s + 1 < nsteps) load((s + 1) * BMM_TK);   // in flight during this step's matrix work
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int ch = kk * 4 + q16;
+                v4i fx[4], fw[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int rx = wm * 64 + i * 16 + t16, rw = wn * 64 + i * 16 + t16;
+                    fx[i] = *(const v4i *)(xs + rx * BMM_TK + ((ch ^ ((rx >> 1) & 7)) << 4));
+                    fw[i] = *(const v4i *)(ws + rw * BMM_TK + ((ch ^ ((rw >> 1) & 7)) << 4));
+                }
+                // lane: column m = t16 of the m tile, rows n = 4 q16 .. + 3 of the n tile (the 16 x 16 layout of epilogue_wave16)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = MmaI8x16::mma(fw[j], fx[i], acc[i][j]);
+            }
+        }
+        __syncthreads();   // the operand tiles are dead: the staging image takes their place
+
+        // Epilogue in two passes of 32 rows per wave.  Image row ir = wm * 32 + (row within the pass) holds output row
+        // m0 + wm * 64 + 32 p + (ir & 31); 16-B chunk c of a row is stored at c ^ (ir & (NC - 1)).
+        const int64_t obase = bt * M * N;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+#pragma unroll
+            for (int ii = 0; ii < 2; ++ii) {
+                const int im = 2 * p + ii, ir = wm * 32 + ii * 16 + t16;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (EB == 4) {
+                        const int c = wn * 16 + j * 4 + q16;
+                        *(v4i *)(lds + ir * RB + ((c ^ (ir & (NC - 1))) << 4)) = bmm_pack16<KIND>(acc[im][j], alpha);
+                    } else {
+                        const int c = wn * 4 + j;
+                        *(uint32_t *)(lds + ir * RB + ((c ^ (ir & (NC - 1))) << 4) + 4 * q16) = bmm_pack4<KIND>(acc[im][j], alpha);
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 64 * NC / 256; ++i) {
+                const int idx = tid + 256 * i, ir = idx / NC, c = idx % NC;
+                const v4i v = *(const v4i *)(lds + ir * RB + ((c ^ (ir & (NC - 1))) << 4));
+                const int64_t m = m0 + (ir >> 5) * 64 + 32 * p + (ir & 31), n = n0 + c * (16 / EB);
+                if (m < M && n < N) bmm_store_chunk<EB>(out, obase + m * N + n, v, N - n, vec);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+constexpr int BMM_NT = 2;   // 16-column MFMA tiles per bmm_i8_m16 block
+
+template <int KIND>
+__global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
+                                                  int64_t K, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec4)
+{
+    constexpr int EB = BmmOut<KIND>::kBytes;
+    __shared__ v4i red[4][BMM_NT][64];   // each wave's partial sums, lane-linear
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t16 = lane & 15, q16 = lane >> 4;
+    const int64_t nks = (K + 63) / 64;
+
+    for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
+        const int64_t bt = id / tiles_n, n0 = (id - bt * tiles_n) * (16 * BMM_NT);
+        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
+        v4i acc[BMM_NT];
+#pragma unroll
+        for (int j = 0; j < BMM_NT; ++j) acc[j] = (v4i){0, 0, 0, 0};
+        // MFMA fragments straight from memory: lane = row t16 (of A: the token; of B: the column n0 + 16 j + t16), 16 k-bytes at 16 q16 of the K step
+        for (int64_t ks = wave; ks < nks; ks += 4) {
+            const int64_t k = ks * 64 + q16 * 16;
+            const v4i fx = load16_guarded(ab, K, t16, M, k, K, fast);
+            v4i fw[BMM_NT];
+#pragma unroll
+            for (int j = 0; j < BMM_NT; ++j) fw[j] = load16_guarded(bb, K, n0 + 16 * j + t16, N, k, K, fast);
+#pragma unroll
+            for (int j = 0; j < BMM_NT; ++j) acc[j] = MmaI8x16::mma(fw[j], fx, acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < BMM_NT; ++j) red[wave][j][lane] = acc[j];
+        __syncthreads();
+        if (wave < BMM_NT) {   // wave j finishes column tile j: exact int32 sum of the four partials, then the epilogue
+            const int j = wave;
+            const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
+            const int64_t m = t16, n = n0 + 16 * j + 4 * q16;
+            if (m < M && n < N) {
+                const int64_t off = bt * M * N + m * N + n;
+                if constexpr (EB == 4) {
+                    const v4i v = bmm_pack16<KIND>(s, alpha);
+                    if (vec4 && n + 4 <= N) {
+                        *(v4i *)((int32_t *)out + off) = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (n + e < N) ((int32_t *)out)[off + e] = v[e];
+                    }
+                } else {
+                    const uint32_t v = bmm_pack4<KIND>(s, alpha);
+                    if (vec4 && n + 4 <= N) {
+                        *(uint32_t *)((int8_t *)out + off) = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (n + e < N) ((int8_t *)out)[off + e] = (int8_t)(v >> (8 * e));
+                    }
+                }
+            }
+        }
+        __syncthreads();   // red is rewritten by the next tile of a grid-stride loop
+    }
+}
+
+static inline bool bmm_narrow(int64_t M) { return M <= 16; }
+
+static inline int64_t bmm_grid(int64_t total) { return total < (int64_t(1) << 30) ? total : (int64_t(1) << 30); }
+
+template <int KIND>
+static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    constexpr int EB = BmmOut<KIND>::kBytes;
+    const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
+    if (bmm_narrow(M)) {
+        const int64_t tiles_n = (N + 16 * BMM_NT - 1) / (16 * BMM_NT), total = batch * tiles_n;
+        const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
+        hipLaunchKernelGGL((bmm_i8_m16<KIND>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, alpha, fast, vec4);
+    } else {
+        const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
+        const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
+        hipLaunchKernelGGL((bmm_i8_t128<KIND>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, alpha, fast,
+                           vec);
+    }
+    return asq_after_launch(s, "asq_bmm_i8");
+}
+
+static inline bool bmm_mul(int64_t x, int64_t y, int64_t &r) { return !__builtin_mul_overflow(x, y, &r); }
+
+}  // namespace asq
+
+using namespace asq;
+
+extern "C" const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind)
+{
+    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || out_kind < ASQ_BMM_S32 || out_kind > ASQ_BMM_S8) return "none";
+    return bmm_narrow(M) ? "m16" : "t128";
+}
+
+extern "C" int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream)
+{
+    const AsqRange range_("asq_bmm_i8");
+    int64_t mn = 0, bmn = 0, mk = 0, bmk = 0, nk = 0, bnk = 0, bytes = 0;
+    ASQ_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, ASQ_ERR_DIM, "asq_bmm_i8: bad dims batch=%lld M=%lld N=%lld K=%lld", (long long)batch,
+                (long long)M, (long long)N, (long long)K);
+    ASQ_REQUIRE(bmm_mul(M, N, mn) && bmm_mul(batch, mn, bmn) && bmm_mul(bmn, 4, bytes) && bmm_mul(M, K, mk) && bmm_mul(batch, mk, bmk) && bmm_mul(N, K, nk) &&
+                    bmm_mul(batch, nk, bnk),
+                ASQ_ERR_DIM, "asq_bmm_i8: size overflows 64 bits (batch=%lld M=%lld N=%lld K=%lld)", (long long)batch, (long long)M, (long long)N, (long long)K);
+    ASQ_REQUIRE(out_kind == ASQ_BMM_S32 || out_kind == ASQ_BMM_F32 || out_kind == ASQ_BMM_S8, ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
+    if (bmn == 0) return ASQ_OK;
+    ASQ_REQUIRE(out != nullptr, ASQ_ERR_NULL, "asq_bmm_i8: NULL out");
+    ASQ_REQUIRE(K == 0 || (a != nullptr && b != nullptr), ASQ_ERR_NULL, "asq_bmm_i8: NULL a / b");
+    ASQ_REQUIRE(out_kind == ASQ_BMM_S8 || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
+    hipStream_t s = (hipStream_t)stream;
+    switch (out_kind) {
+    case ASQ_BMM_S32: return launch_bmm<ASQ_BMM_S32>(a, b, out, batch, M, N, K, alpha, s);
+    case ASQ_BMM_F32: return launch_bmm<ASQ_BMM_F32>(a, b, out, batch, M, N, K, alpha, s);
+    default: return launch_bmm<ASQ_BMM_S8>(a, b, out, batch, M, N, K, alpha, s);
+    }
+}

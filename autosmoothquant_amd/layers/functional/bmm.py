@@ -1,0 +1,12 @@
+"""Functional batched int8 matmuls (reference autosmoothquant/layers/functional/bmm.py)."""
+from ..._CUDA import bmm_s8t_s8n_s8t, bmm_s8t_s8n_s32t
+
+
+def bmm_i8_o8(a, b, scale):
+    # a: [B, M, K] int8, b: [B, N, K] int8, scale: float -> [B, M, N] int8 = sat_i8(rne(scale * (a . b^T)))
+    return bmm_s8t_s8n_s8t(a, b, scale)
+
+
+def bmm_i8_o32(a, b):
+    # a: [B, M, K] int8, b: [B, N, K] int8 -> [B, M, N] int32 = a . b^T
+    return bmm_s8t_s8n_s32t(a, b)

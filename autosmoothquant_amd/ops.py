@@ -937,6 +937,35 @@ def gemm_kernel_name(M, N, K):
     return L.lib().asq_gemm_kernel_name(M, N, K).decode()
 
 
+_BMM_KIND = {torch.int32: L.ASQ_BMM_S32, torch.float32: L.ASQ_BMM_F32, torch.int8: L.ASQ_BMM_S8}
+_BMM_DTYPE = {code: dt for dt, code in _BMM_KIND.items()}
+
+
+def bmm_i8(a, b, out_kind, alpha=1.0):
+    """Batched int8 A . B^T (reference bmm_s8t_s8n_{s32t,f32t,s8t}, csrc/kernels/bmm.cu:10-211): a int8 [B, M, K], b int8 [B, N, K] ->
+    a new [B, M, N] tensor on the current stream.  out_kind: torch.int32 / L.ASQ_BMM_S32 (the exact accumulator; alpha ignored),
+    torch.float32 / L.ASQ_BMM_F32 (alpha * float(acc)), torch.int8 / L.ASQ_BMM_S8 (sat_i8(rne(alpha * float(acc)))); alpha reaches the kernel as fp32."""
+    _dev(a, "a"), _dev(b, "b")
+    if a.dtype != torch.int8 or b.dtype != torch.int8:
+        raise RuntimeError(f"expected int8 a and b, got {a.dtype} and {b.dtype}")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
+        raise ValueError(f"shape mismatch: a {tuple(a.shape)} must be [B, M, K] and b {tuple(b.shape)} [B, N, K]")
+    kind = _BMM_KIND.get(out_kind, out_kind) if isinstance(out_kind, torch.dtype) else out_kind
+    if kind not in _BMM_DTYPE:
+        raise ValueError(f"out_kind must be torch.int32, torch.float32 or torch.int8 (or an ASQ_BMM_* code), got {out_kind!r}")
+    dev = _same_device(a, b)
+    B, M, K = a.shape
+    N = b.shape[1]
+    out = torch.empty((B, M, N), dtype=_BMM_DTYPE[kind], device=dev)
+    with _on(dev):
+        L.check(L.lib().asq_bmm_i8(a.data_ptr(), b.data_ptr(), out.data_ptr(), kind, B, M, N, K, float(alpha), _stream(a)), "asq_bmm_i8")
+    return out
+
+
+def bmm_kernel_name(batch, M, N, K, out_kind=L.ASQ_BMM_F32):
+    return L.lib().asq_bmm_kernel_name(batch, M, N, K, _BMM_KIND.get(out_kind, out_kind) if isinstance(out_kind, torch.dtype) else out_kind).decode()
+
+
 def linear_fp8_grouped(xq, a_scale, w, w_scale_group, group_offsets, out_dtype, bias=None):
     """ngroups independent e4m3 linears in one launch (Mixtral experts, FP8LinearDynamic math).  xq float8_e4m3fn [M,K]
     rows sorted by group, a_scale f32 [M] or [M,1] (per-token, device), w float8_e4m3fn [G,N,K], w_scale_group f32 [G]

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ASQ_VERSION 126 /* 0.1.8: + asq_rmsnorm, asq_silu_mul (caller-side glue of the reference's module composition: the norm and the gated activation as one pass each, floating outputs); 0.1.7: + asq_fp8_grouped_gate_up_supported, asq_linear_fp8_grouped_gate_up (FP8LinearDynamic experts' w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.6: + asq_rope (caller-side glue: rotary embedding of a q / k projection's output in one pass); 0.1.5: + asq_silu_mul_quantize_fp8 (SiLU * up fused with the per-token e4m3 quantiser of the FP8 linear behind it); 0.1.4: + asq_linear_w8a8_gate_up_q8 (gate || up with an int8-out epilogue for per-tensor consumers); 0.1.3: + asq_grouped_gate_up_supported, asq_linear_w8a8_grouped_gate_up (Mixtral's w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.2: + asq_forward_fused_supported, asq_linear_w8a8_forward_fused (the one-launch forward for decode-sized inputs; asq_linear_w8a8_forward takes it
+#define ASQ_VERSION 126 /* (0.1.8 also adds asq_bmm_i8, asq_bmm_kernel_name: the batched int8 matmuls; purely additive, so the number stays -- a library without them is still refused, the loader binds every declared symbol); 0.1.8: + asq_rmsnorm, asq_silu_mul (caller-side glue of the reference's module composition: the norm and the gated activation as one pass each, floating outputs); 0.1.7: + asq_fp8_grouped_gate_up_supported, asq_linear_fp8_grouped_gate_up (FP8LinearDynamic experts' w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.6: + asq_rope (caller-side glue: rotary embedding of a q / k projection's output in one pass); 0.1.5: + asq_silu_mul_quantize_fp8 (SiLU * up fused with the per-token e4m3 quantiser of the FP8 linear behind it); 0.1.4: + asq_linear_w8a8_gate_up_q8 (gate || up with an int8-out epilogue for per-tensor consumers); 0.1.3: + asq_grouped_gate_up_supported, asq_linear_w8a8_grouped_gate_up (Mixtral's w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.2: + asq_forward_fused_supported, asq_linear_w8a8_forward_fused (the one-launch forward for decode-sized inputs; asq_linear_w8a8_forward takes it
                            * by itself where it wins); ASQ_ROCTX=1 ranges.  0.1.1: + offset operand images (asq_*_off); workspace sizes include the 8 KiB header
                            * (asq_workspace_init is mandatory for a workspace handed to a GEMM entry point); asq_silu_mul_quantize's `per_token` is a bit field (bit 0
                            * per-token, ASQ_SILU_FAST) */
@@ -385,6 +385,22 @@ int asq_cast_e5m2(const void *x, int x_dtype, uint8_t *xq, int64_t n, void *stre
 int asq_quantize_mxfp8(const void *x, int x_dtype, uint8_t *xq, uint8_t *scales, int64_t M, int64_t K, void *stream);
 int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *wq, const uint8_t *w_scales, void *out, int out_dtype,
                      int64_t M, int64_t N, int64_t K, const float *bias, void *stream);
+
+/* ---- batched int8 matmuls: the reference's bmm_s8t_s8n_s32t / _f32t / _s8t (csrc/kernels/bmm.cu:10-211, include/bmm.h; bindings.cpp:16-19),
+ * behind layers/nn/bmm.py (BMM_S8T_S8N_S8T / _F32T / _S32T) and layers/functional/bmm.py (bmm_i8_o8, bmm_i8_o32).
+ *   a int8 [batch, M, K], b int8 [batch, N, K], out [batch, M, N]: all dense;  acc[i, m, n] = sum_k a[i, m, k] * b[i, n, k]  (exact int32, wraps)
+ *   out_kind: see below; alpha is the reference's `float alpha` (CUTLASS LinearCombination / LinearCombinationClamp with beta = 0).
+ * Bit-identical per batch to asq_gemm_i8_i32 (S32) and asq_gemm_i8_i8(alpha, beta = 0) (S8).  Any batch, M, N, K >= 0 and any alignment of a / b (the
+ * reference needs K % 16 == 0; K % 16 == 0 with 16-B aligned operands takes the unguarded load path); K = 0 writes alpha * 0.0 (S32: 0).
+ * ASQ_ERR_DIM: a negative size or batch * M * N (x 4 bytes), batch * M * K, batch * N * K overflowing 64 bits;  ASQ_ERR_DTYPE: unknown out_kind;
+ * ASQ_ERR_NULL: out NULL on a non-empty output, a / b NULL with K > 0;  ASQ_ERR_ALIGN: out not aligned to its element.  An empty output is a no-op.
+ * No workspace.  asq_bmm_kernel_name: "m16" (M <= 16: one 16-row tile, B streamed into the matrix cores), "t128" (128 x 128 tiles), "none" (empty / invalid). */
+#define ASQ_BMM_S32 0 /* bmm_s8t_s8n_s32t: out int32 = acc (alpha ignored)           */
+#define ASQ_BMM_F32 1 /* bmm_s8t_s8n_f32t: out float = alpha * float(acc)            */
+#define ASQ_BMM_S8 2  /* bmm_s8t_s8n_s8t : out int8  = sat_i8(rne(alpha*float(acc))) */
+int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind,
+               int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream);
+const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind);
 
 /* ---- introspection for tests / bench: which GEMM kernel the dispatcher picks for a shape (aligned operands):
  * "skinny" (weight streaming), "p8q" (128x128x128 tiles), "p8h" (128x256x128 tiles), "p16" (256x256x128 tiles, 8 waves, on v_mfma_i32_16x16x64_i8;
