@@ -5,7 +5,7 @@ TAG=${1:-r3}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$ROOT/gpurun_out/cfg_$TAG; mkdir -p $O
 cd $ROOT
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 $B --workload gemm4096 > $O/gemm4096.json 2> $O/err.txt
 $B --workload cfg1_int8linear_m4 --dtype f32 --steps 200 > $O/cfg1_eager.json 2>> $O/err.txt
 $B --workload cfg1_int8linear_m4 --dtype f32 --steps 200 --graph > $O/cfg1_graph.json 2>> $O/err.txt

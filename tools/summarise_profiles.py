@@ -68,7 +68,7 @@ bench = last_json_line(os.path.join(src, "bench.json"))
 import hashlib
 out = {
     "library_sha256": hashlib.sha256(open(os.path.join(root, "autosmoothquant_amd", "libasq_hip.so"), "rb").read()).hexdigest(),   # bench.py reports these bytes only for THIS build of the library
-    "command": "rocprofv3 --kernel-trace --pmc <C> --output-format csv -- python bench.py --no-cpu-baseline --no-cfg3 --steps 5 --warmup 2  (one pass per counter, C in {FETCH_SIZE, WRITE_SIZE})",
+    "command": "rocprofv3 --kernel-trace --pmc <C> --output-format csv -- python bench.py --full --no-cpu-baseline --no-cfg3 --steps 5 --warmup 2  (one pass per counter, C in {FETCH_SIZE, WRITE_SIZE})",
     "units": "rocprofv3 reports FETCH_SIZE/WRITE_SIZE in KiB per dispatch",
     "gfx950_correction": "FETCH_SIZE x2 (MI355X_MICROARCH.md 'HBM'); check: quant_flat_vec reads exactly M*K*2 B and writes M*K B",
     "workload": bench["config"]["workload"],
@@ -104,7 +104,7 @@ for counter in ("MfmaUtil", "SQ_INSTS_VALU_MFMA_I8", "SQ_LDS_BANK_CONFLICT", "SQ
     except (IndexError, KeyError):
         pass
 if extra:
-    json.dump({"command": "rocprofv3 --kernel-trace --pmc <C> -- python bench.py --no-cpu-baseline --no-cfg3 --steps 5 --warmup 2 (one pass per counter)",
+    json.dump({"command": "rocprofv3 --kernel-trace --pmc <C> -- python bench.py --full --no-cpu-baseline --no-cfg3 --steps 5 --warmup 2 (one pass per counter)",
                "notes": "MfmaUtil = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE * SIMD_NUM) in percent (rocprofv3 derived metric); "
                         "SQ_INSTS_VALU_MFMA_I8: 4096^3 needs 2*4096^3 / (2*16*16*64) = 4194304 wave-level v_mfma_i32_16x16x64_i8 (gemm_i8_p16; 2097152 of the 32x32x32 form for gemm_i8_p8)",
                "kernels": extra}, open(os.path.join(dst, f"{tag}_pmc_mfma_lds.json"), "w"), indent=1)
@@ -118,7 +118,7 @@ for t in ("cfg3", "cfg3_fused"):
     rows = list(csv.DictReader(open(fs[0])))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     with open(os.path.join(dst, f"{tag}_{t}_kernel_stats.txt"), "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --stats -- python bench.py --workload llama7b_decoder_b32_s2048 {'--fuse-norm --fuse-qkv ' if 'fused' in t else ''}--steps 2 --warmup 1 --no-cpu-baseline\n")
+        f.write(f"# rocprofv3 --kernel-trace --stats -- python bench.py --full --workload llama7b_decoder_b32_s2048 {'--fuse-norm --fuse-qkv ' if 'fused' in t else ''}--steps 2 --warmup 1 --no-cpu-baseline\n")
         f.write("# 3 forwards + set-up + the dominant-kernel timing batches (gate GEMM at M = 8192: warm launches + the settle time + 20 x 50 timed launches, on images and on plain operands); share of total GPU kernel time\n")
         for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:24]:
             f.write("%5.1f%%  calls %6s  avg %9.1f us  %s\n" % (float(r["TotalDurationNs"]) / tot * 100, r["Calls"], float(r["AverageNs"]) / 1e3, re.sub(r"\(.*", "", r["Name"])[:110]))
