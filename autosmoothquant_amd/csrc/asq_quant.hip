@@ -557,21 +557,25 @@ template <int DT> __device__ __forceinline__ v4i vec_pack(const float (&f)[ElemT
     }
 }
 
-// ADD: the residual-add form (the reference's dq_add_layernorm_q, csrc/kernels/fused.cu:5-25, with a floating `x`
+// ADD = 1: the residual-add form (the reference's dq_add_layernorm_q, csrc/kernels/fused.cu:5-25, with a floating `x`
 // -- here the previous GEMM's epilogue has already dequantised): h = dt(x + residual) is written to `hout` (the
 // new residual stream) and normalised + quantised in the same pass.
-template <int DT, int NV, bool LAYERNORM, bool PER_TOKEN, bool ADD>
+// ADD = 2: the reference's own dq_add_layernorm_q on the int32 accumulator: h = dt(fma(x_scale, f32(dt(f32(x))), f32(residual))), which is
+// torch.add(residual, x, alpha=x_scale) -- x converted as torch converts it (to fp32, then to dt; each RNE), then one fp32 multiply-add.
+// The int32 row is 4 B per element: VEC / 4 16-B loads per 16 B of residual.
+template <int DT, int NV, bool LAYERNORM, bool PER_TOKEN, int ADD>
 // (xv, resv and hout carry NO __restrict__: the API allows h_out to alias residual or x -- the residual stream updated in place -- and an aliased
 // restrict pointer is undefined behaviour even though every thread loads a vector before it stores the same one)
 __global__ void __launch_bounds__(256) norm_quant_cached(const void *xv, const void *resv, void *hout,
                                                          const void *__restrict__ wv, const void *__restrict__ bv, float eps,
-                                                         int8_t *__restrict__ xq, float *__restrict__ s_row, int K, int32_t *__restrict__ row_off, int C)
+                                                         int8_t *__restrict__ xq, float *__restrict__ s_row, int K, int32_t *__restrict__ row_off, int C,
+                                                         float x_scale)
 {
     constexpr int VEC = ElemT<DT>::VEC;
     __shared__ float red[4];
     const int64_t row = blockIdx.x;
     const int64_t rowoff = row * (int64_t)K * (16 / VEC);
-    const char *xrow = (const char *)xv + rowoff;
+    const char *xrow = (const char *)xv + (ADD == 2 ? row * (int64_t)K * 4 : rowoff);
     const int nvec = K / VEC;
     float f[NV][VEC];
     float sum = 0.f, sq = 0.f;
@@ -579,8 +583,21 @@ __global__ void __launch_bounds__(256) norm_quant_cached(const void *xv, const v
     for (int i = 0; i < NV; ++i) {
         const int idx = i * 256 + threadIdx.x;
         if (idx < nvec) {
-            vec_unpack<DT>(*(const v4i *)(xrow + (int64_t)idx * 16), f[i]);
-            if constexpr (ADD) {
+            if constexpr (ADD == 2) {
+                float r[VEC];
+                vec_unpack<DT>(*(const v4i *)((const char *)resv + rowoff + (int64_t)idx * 16), r);
+#pragma unroll
+                for (int h = 0; h < VEC / 4; ++h) {
+                    const v4i a = *(const v4i *)(xrow + (int64_t)idx * (4 * VEC) + 16 * h);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)  // torch.add(residual, x, alpha=x_scale) in dt
+                        f[i][4 * h + j] = ElemT<DT>::round(__fmaf_rn(x_scale, ElemT<DT>::round((float)a[j]), r[4 * h + j]));
+                }
+                *(v4i *)((char *)hout + rowoff + (int64_t)idx * 16) = vec_pack<DT>(f[i]);
+            } else {
+                vec_unpack<DT>(*(const v4i *)(xrow + (int64_t)idx * 16), f[i]);
+            }
+            if constexpr (ADD == 1) {
                 float r[VEC];
                 vec_unpack<DT>(*(const v4i *)((const char *)resv + rowoff + (int64_t)idx * 16), r);
 #pragma unroll
@@ -757,14 +774,14 @@ template <int DT, bool FAST> __global__ void __launch_bounds__(256) silu_mul_fla
     }
 }
 
-template <int DT, bool LN, bool PT, bool ADD = false>
+template <int DT, bool LN, bool PT, int ADD = 0>
 int launch_norm_quant(const void *x, const void *w, const void *b, float eps, int8_t *xq, float *s_row, int64_t M, int64_t K, hipStream_t s,
-                      const void *res = nullptr, void *hout = nullptr, int32_t *row_off = nullptr, int C = 0)
+                      const void *res = nullptr, void *hout = nullptr, int32_t *row_off = nullptr, int C = 0, float x_scale = 1.0f)
 {
     constexpr int VEC = ElemT<DT>::VEC;
     const int64_t nvec = K / VEC;
     dim3 grid((unsigned)M), block(256);
-#define ASQ_NQ(NV) hipLaunchKernelGGL((norm_quant_cached<DT, NV, LN, PT, ADD>), grid, block, 0, s, x, res, hout, w, b, eps, xq, s_row, (int)K, row_off, C)
+#define ASQ_NQ(NV) hipLaunchKernelGGL((norm_quant_cached<DT, NV, LN, PT, ADD>), grid, block, 0, s, x, res, hout, w, b, eps, xq, s_row, (int)K, row_off, C, x_scale)
     if (nvec <= 256 * 1) ASQ_NQ(1);
     else if (nvec <= 256 * 2) ASQ_NQ(2);
     else if (nvec <= 256 * 4) ASQ_NQ(4);
@@ -1035,10 +1052,10 @@ static int add_norm_quantize_impl(const void *x, const void *residual, void *h_o
     hipStream_t s = (hipStream_t)stream;
     const int C = offset_cx();
 #define ASQ_ANQ(DT_)                                                                                                                       \
-    (bias ? (per_token ? launch_norm_quant<DT_, true, true, true>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)               \
-                       : launch_norm_quant<DT_, true, false, true>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C))             \
-          : (per_token ? launch_norm_quant<DT_, false, true, true>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)              \
-                       : launch_norm_quant<DT_, false, false, true>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)))
+    (bias ? (per_token ? launch_norm_quant<DT_, true, true, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)               \
+                       : launch_norm_quant<DT_, true, false, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C))             \
+          : (per_token ? launch_norm_quant<DT_, false, true, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)              \
+                       : launch_norm_quant<DT_, false, false, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)))
     switch (x_dtype) {
     case ASQ_F32: return ASQ_ANQ(ASQ_F32);
     case ASQ_F16: return ASQ_ANQ(ASQ_F16);
@@ -1059,6 +1076,26 @@ extern "C" int asq_add_norm_quantize_off(const void *x, const void *residual, vo
     ASQ_REQUIRE(M == 0 || (row_off != nullptr && ((uintptr_t)row_off & 7) == 0), ASQ_ERR_NULL, "asq_add_norm_quantize_off: row_off NULL or not 8-B aligned");
     ASQ_REQUIRE(K <= 65536, ASQ_ERR_DIM, "asq_add_norm_quantize_off: K <= 65536");
     return add_norm_quantize_impl(x, residual, h_out, x_dtype, weight, bias, eps, per_token, xq, s_row, row_off, M, K, stream);
+}
+
+extern "C" int asq_dq_add_layernorm_q(const int32_t *x, float x_scale, const void *residual, void *h_out, int dtype, const void *gamma, const void *beta,
+                                      float eps, int8_t *q, int64_t M, int64_t K, void *stream)
+{
+    const AsqRange range_("asq_dq_add_layernorm_q");
+    ASQ_REQUIRE(M >= 0 && K > 0 && M < (1ll << 31), ASQ_ERR_DIM, "asq_dq_add_layernorm_q: bad dims M=%lld K=%lld", (long long)M, (long long)K);
+    ASQ_REQUIRE(dtype == ASQ_F32 || dtype == ASQ_F16 || dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_dq_add_layernorm_q: bad dtype %d", dtype);
+    if (M == 0) return ASQ_OK;
+    ASQ_REQUIRE(x && residual && h_out && gamma && beta && q, ASQ_ERR_NULL, "asq_dq_add_layernorm_q: NULL pointer");
+    const int vec = dtype == ASQ_F32 ? 4 : 8;
+    ASQ_REQUIRE(K % vec == 0 && K / vec <= 256 * 8, ASQ_ERR_DIM, "asq_dq_add_layernorm_q: K must be a multiple of %d and <= %d", vec, 256 * 8 * vec);
+    ASQ_REQUIRE(((((uintptr_t)x | (uintptr_t)residual | (uintptr_t)h_out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) && (((uintptr_t)q & (vec - 1)) == 0),
+                ASQ_ERR_ALIGN, "asq_dq_add_layernorm_q: x / residual / h_out / gamma / beta must be 16-B aligned, q %d-B aligned", vec);
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+    case ASQ_F32: return launch_norm_quant<ASQ_F32, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
+    case ASQ_F16: return launch_norm_quant<ASQ_F16, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
+    default: return launch_norm_quant<ASQ_BF16, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
+    }
 }
 
 static int silu_mul_quantize_impl(const void *gate, const void *up, int x_dtype, int per_token, float quant_scale, int8_t *xq, float *s_row, int32_t *row_off,

@@ -966,6 +966,79 @@ def bmm_kernel_name(batch, M, N, K, out_kind=L.ASQ_BMM_F32):
     return L.lib().asq_bmm_kernel_name(batch, M, N, K, _BMM_KIND.get(out_kind, out_kind) if isinstance(out_kind, torch.dtype) else out_kind).decode()
 
 
+# asq_linear_i8_bias kinds -> (bias dtype, out dtype)
+_LIN_BIAS = {L.ASQ_LIN_B32_O32: (torch.int32, torch.int32), L.ASQ_LIN_B32_O32_SCALED: (torch.int32, torch.int32),
+             L.ASQ_LIN_BF32_OF32: (torch.float32, torch.float32), L.ASQ_LIN_B8_O8: (torch.int8, torch.int8), L.ASQ_LIN_RELU_B8_O8: (torch.int8, torch.int8)}
+
+
+def _tensor(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    return t
+
+
+def linear_i8_bias(x, w, bias, kind, alpha=1.0, beta=1.0):
+    """int8 linear with a fused [N] bias epilogue (reference csrc/kernels/linear.cu:13-491): x int8 [M,K], w int8 [N,K], bias [N] in the kind's
+    bias dtype (int32 for ASQ_LIN_B32_O32[_SCALED], float32 for ASQ_LIN_BF32_OF32, int8 for ASQ_LIN_[RELU_]B8_O8) -> a new [M,N] tensor on the
+    current stream.  v = fl(fl(alpha * float(acc)) + fl(beta * float(bias[n]))), the add skipped when beta == 0; include/asq_hip.h has the table.
+    The bias may live on the host (it is copied to the device, as the reference's bias.to(device))."""
+    _tensor(x, "input"), _tensor(w, "weight"), _tensor(bias, "bias")
+    if kind not in _LIN_BIAS:
+        raise ValueError(f"kind must be one of the ASQ_LIN_* codes 0..4, got {kind!r}")
+    bias_dt, out_dt = _LIN_BIAS[kind]
+    if x.dtype != torch.int8 or w.dtype != torch.int8:
+        raise RuntimeError(f"expected int8 input and weight, got {x.dtype} and {w.dtype}")
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"shape mismatch: input {tuple(x.shape)} must be [M, K] and weight {tuple(w.shape)} [N, K]")
+    M, K = x.shape
+    N = w.shape[0]
+    if bias.dtype != bias_dt or bias.dim() != 1 or bias.shape[0] != N:
+        raise ValueError(f"bias must be a [{N}] {bias_dt} tensor for this kind, got {tuple(bias.shape)} {bias.dtype}")
+    _dev(x, "input"), _dev(w, "weight")
+    dev = _same_device(x, w)
+    if bias.device.type == "cpu":
+        bias = bias.to(dev)
+    elif bias.device != dev:
+        raise RuntimeError(f"bias is on {bias.device}, input on {dev}")
+    bias = bias.contiguous()
+    out = torch.empty((M, N), dtype=out_dt, device=dev)
+    with _on(dev):
+        ws, n = _gemm_ws(M, N, K, dev, _stream(x))
+        L.check(L.lib().asq_linear_i8_bias(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), kind, M, N, K, float(alpha), float(beta),
+                                           _ptr(ws), n, _stream(x)), "asq_linear_i8_bias")
+    return out
+
+
+def dq_add_layernorm_q(x, x_scale, residual, gamma, beta, eps=1e-5):
+    """The reference's dq_add_layernorm_q (csrc/kernels/fused.cu:5-25) in one pass: x int32 [..., K], residual [..., K] and gamma, beta [K] of
+    one float dtype.  Returns (residual_output = torch.add(residual, x, alpha=x_scale) in residual's dtype, ln_output int8 = the rounded, clamped
+    LayerNorm of residual_output).  Everything must be contiguous and 16-B aligned, K a multiple of 4 (fp32) / 8 (fp16, bf16) within
+    asq_add_norm_quantize's limit: this raises instead of copying (the _CUDA wrapper copies)."""
+    for t, name in ((x, "input"), (residual, "residual"), (gamma, "gamma"), (beta, "beta")):
+        _tensor(t, name)
+    if x.dtype != torch.int32:
+        raise RuntimeError(f"expected an int32 input, got {x.dtype}")
+    if residual.dtype not in _DT:
+        raise RuntimeError(f"residual must be float32, float16 or bfloat16, got {residual.dtype}")
+    if gamma.dtype != residual.dtype or beta.dtype != residual.dtype:
+        raise ValueError(f"gamma and beta must have the residual's dtype {residual.dtype}, got {gamma.dtype} and {beta.dtype}")
+    if x.dim() < 1 or tuple(x.shape) != tuple(residual.shape):
+        raise ValueError(f"shape mismatch: input {tuple(x.shape)} and residual {tuple(residual.shape)} must be equal [..., K]")
+    K = x.shape[-1]
+    if gamma.dim() != 1 or beta.dim() != 1 or gamma.shape[0] != K or beta.shape[0] != K:
+        raise ValueError(f"gamma and beta must be [{K}], got {tuple(gamma.shape)} and {tuple(beta.shape)}")
+    for t, name in ((x, "input"), (residual, "residual"), (gamma, "gamma"), (beta, "beta")):
+        _dev(t, name)
+    dev = _same_device(x, residual, gamma, beta)
+    h = torch.empty_like(residual)
+    q = torch.empty(tuple(x.shape), dtype=torch.int8, device=dev)
+    M = x.numel() // K if K else 0
+    with _on(dev):
+        L.check(L.lib().asq_dq_add_layernorm_q(x.data_ptr(), float(x_scale), residual.data_ptr(), h.data_ptr(), _DT[residual.dtype], gamma.data_ptr(),
+                                               beta.data_ptr(), float(eps), q.data_ptr(), M, K, _stream(x)), "asq_dq_add_layernorm_q")
+    return h, q
+
+
 def linear_fp8_grouped(xq, a_scale, w, w_scale_group, group_offsets, out_dtype, bias=None):
     """ngroups independent e4m3 linears in one launch (Mixtral experts, FP8LinearDynamic math).  xq float8_e4m3fn [M,K]
     rows sorted by group, a_scale f32 [M] or [M,1] (per-token, device), w float8_e4m3fn [G,N,K], w_scale_group f32 [G]

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ASQ_VERSION 126 /* (0.1.8 also adds asq_bmm_i8, asq_bmm_kernel_name: the batched int8 matmuls; purely additive, so the number stays -- a library without them is still refused, the loader binds every declared symbol); 0.1.8: + asq_rmsnorm, asq_silu_mul (caller-side glue of the reference's module composition: the norm and the gated activation as one pass each, floating outputs); 0.1.7: + asq_fp8_grouped_gate_up_supported, asq_linear_fp8_grouped_gate_up (FP8LinearDynamic experts' w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.6: + asq_rope (caller-side glue: rotary embedding of a q / k projection's output in one pass); 0.1.5: + asq_silu_mul_quantize_fp8 (SiLU * up fused with the per-token e4m3 quantiser of the FP8 linear behind it); 0.1.4: + asq_linear_w8a8_gate_up_q8 (gate || up with an int8-out epilogue for per-tensor consumers); 0.1.3: + asq_grouped_gate_up_supported, asq_linear_w8a8_grouped_gate_up (Mixtral's w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.2: + asq_forward_fused_supported, asq_linear_w8a8_forward_fused (the one-launch forward for decode-sized inputs; asq_linear_w8a8_forward takes it
+#define ASQ_VERSION 126 /* (0.1.9: + asq_linear_i8_bias, asq_dq_add_layernorm_q: the reference's bias-epilogue int8 linears and its int32-input residual-add LayerNorm; purely additive, the number stays); (0.1.8 also adds asq_bmm_i8, asq_bmm_kernel_name: the batched int8 matmuls; purely additive, so the number stays -- a library without them is still refused, the loader binds every declared symbol); 0.1.8: + asq_rmsnorm, asq_silu_mul (caller-side glue of the reference's module composition: the norm and the gated activation as one pass each, floating outputs); 0.1.7: + asq_fp8_grouped_gate_up_supported, asq_linear_fp8_grouped_gate_up (FP8LinearDynamic experts' w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.6: + asq_rope (caller-side glue: rotary embedding of a q / k projection's output in one pass); 0.1.5: + asq_silu_mul_quantize_fp8 (SiLU * up fused with the per-token e4m3 quantiser of the FP8 linear behind it); 0.1.4: + asq_linear_w8a8_gate_up_q8 (gate || up with an int8-out epilogue for per-tensor consumers); 0.1.3: + asq_grouped_gate_up_supported, asq_linear_w8a8_grouped_gate_up (Mixtral's w1 || w3 as one grouped launch with the SiLU * up epilogue); 0.1.2: + asq_forward_fused_supported, asq_linear_w8a8_forward_fused (the one-launch forward for decode-sized inputs; asq_linear_w8a8_forward takes it
                            * by itself where it wins); ASQ_ROCTX=1 ranges.  0.1.1: + offset operand images (asq_*_off); workspace sizes include the 8 KiB header
                            * (asq_workspace_init is mandatory for a workspace handed to a GEMM entry point); asq_silu_mul_quantize's `per_token` is a bit field (bit 0
                            * per-token, ASQ_SILU_FAST) */
@@ -401,6 +401,33 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
 int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind,
                int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream);
 const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind);
+
+/* ---- int8 linears with a fused bias epilogue: the reference's linear_a8_w8_{b32_o32, b32_o32_with_scaling, bfp32_ofp32, b8_o8} and
+ * linear_relu_a8_w8_b8_o8 (csrc/kernels/linear.cu:13-491, bindings.cpp:5-15; CUTLASS GEMMs with a LinearCombination epilogue over a broadcast bias).
+ *   x int8 [M,K], w int8 [N,K], bias [N] in the kind's bias dtype, out [M,N] dense;  acc = x . w^T (exact int32, wraps as asq_gemm_i8_i32)
+ *   v = fl(fl(alpha * float(acc)) + fl(beta * float(bias[n])))  -- two roundings, as asq_gemm_i8_i8 / asq_linear_w8a8; the add is skipped when beta == 0
+ *   (a non-finite bias is then ignored and an fp32 -0.0 kept).  ASQ_LIN_B8_O8 equals asq_gemm_i8_i8 over an [M,N] image of the bias bit for bit;
+ *   ASQ_LIN_BF32_OF32 with beta = 1 equals asq_linear_w8a8(ASQ_F32, s_scalar = alpha, bias).  Any M, N, K >= 0 (K = 0: acc = 0) and any K (the
+ *   reference's CUTLASS kernels need K % 16 == 0).  workspace as asq_gemm_i8_i32 (optional, asq_gemm_workspace_bytes, asq_workspace_init).
+ * ASQ_ERR_DIM: a negative or >= 2^31 size, or M * N * 4 overflowing 64 bits;  ASQ_ERR_DTYPE: unknown kind;  an empty output is a no-op;
+ * ASQ_ERR_NULL: out / bias NULL, x / w NULL with K > 0;  ASQ_ERR_ALIGN: out / bias of a 4-byte kind not 4-B aligned. */
+#define ASQ_LIN_B32_O32 0        /* int32 bias -> int32: acc + bias[n] (two's-complement wrap; alpha, beta ignored) */
+#define ASQ_LIN_B32_O32_SCALED 1 /* int32 bias -> int32: sat_i32(rne(v))                                          */
+#define ASQ_LIN_BF32_OF32 2      /* fp32 bias  -> fp32:  v                                                        */
+#define ASQ_LIN_B8_O8 3          /* int8 bias  -> int8:  sat_i8(rne(v))                                           */
+#define ASQ_LIN_RELU_B8_O8 4     /* int8 bias  -> int8:  sat_i8(rne(max(v, 0)))                                   */
+int asq_linear_i8_bias(const int8_t *x, const int8_t *w, const void *bias, void *out, int kind,
+                       int64_t M, int64_t N, int64_t K, float alpha, float beta,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* The reference's dq_add_layernorm_q (csrc/kernels/fused.cu:5-25, layers/functional/fused.py:5-25) on the int32 accumulator itself:
+ *   h_out = torch.add(residual, x, alpha=x_scale) = dtype(fma(x_scale, f32(dtype(f32(x))), f32(residual)))   (x converted as torch converts it:
+ *           to fp32, then to dtype, each RNE -- fp16 turns |x| > 65519 into inf -- then ONE fp32 multiply-add)
+ *   q     = int8(clamp(rne(LayerNorm(h_out; gamma, beta, eps))))   exactly asq_add_norm_quantize's per-tensor LayerNorm path (oracle/n1.py restates it)
+ * x int32 [M,K]; residual, h_out [M,K], gamma, beta [K] of dtype (ASQ_F32 / ASQ_F16 / ASQ_BF16); h_out may alias residual.  Limits as
+ * asq_add_norm_quantize: K % vec == 0 and K <= 2048 * vec (vec = 4 for fp32, 8 otherwise), every pointer 16-B aligned (q vec-B).  M = 0 is a no-op. */
+int asq_dq_add_layernorm_q(const int32_t *x, float x_scale, const void *residual, void *h_out, int dtype,
+                           const void *gamma, const void *beta, float eps, int8_t *q, int64_t M, int64_t K, void *stream);
 
 /* ---- introspection for tests / bench: which GEMM kernel the dispatcher picks for a shape (aligned operands):
  * "skinny" (weight streaming), "p8q" (128x128x128 tiles), "p8h" (128x256x128 tiles), "p16" (256x256x128 tiles, 8 waves, on v_mfma_i32_16x16x64_i8;
