@@ -6,7 +6,7 @@
 //   ASQ_BMM_F32: out = alpha * float(acc)                             EpiDequant<ASQ_F32>::one with the scalar scale: one fp32 product
 //   ASQ_BMM_S8 : out = sat_i8(rne(alpha * float(acc)))                EpiI8::one with beta = 0 (asq_gemm_i8_i8)
 //
-// Two kernels, both on v_mfma_i32_16x16x64_i8 (MmaI8x16), both over ONE 1-D grid of (batch, M tile, N tile), batch-major with the N tile fastest and
+// Two kernels for the plain kinds, both on v_mfma_i32_16x16x64_i8 (MmaI8x16), both over ONE 1-D grid of (batch, M tile, N tile), batch-major with the N tile fastest and
 // XCD-remapped, so neighbouring workgroups of one XCD share a batch's panels in its L2; a grid-stride loop covers any tile count:
 //   bmm_i8_t128  128 x 128 output tiles, 4 waves of 64 x 64, K in steps of 128 through a 32 KiB LDS tile with one K step prefetched in registers.
 //                The epilogue is what bounds the prefill shapes (QK^T: 537 MB of f32 out against 34 GOP): finished values go through the same LDS
@@ -14,6 +14,7 @@
 //                row, 128 B per int8 row, two rows per wave store instruction for 4-byte outputs, eight for int8.
 //   bmm_i8_m16   M <= 16 (decode): one 16-row MFMA tile, 32 output columns per block; each wave streams its share of the K steps of B straight into
 //                MFMA fragments with 16-B loads (no LDS for the operands, no 128-row padding), the four waves' partial sums meet in LDS.
+//   bmm_i8_sm128 the softmax kinds (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]): a block owns 128 rows of a batch and walks B twice; see below.
 // Loads: unguarded 16-B loads when K % 16 == 0 and the operands are 16-B aligned, otherwise load16_guarded's zero-filled byte path (any K, any
 // alignment).  Every offset is 64-bit.  No workspace, no split-K across workgroups.
 #include "asq_gemm_kernels.h"
@@ -232,6 +233,234 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
     }
 }
 
+// ---- ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]: out = int8(rne(127 * softmax_row(alpha * acc))) -------------------------------------------
+// bmm_i8_sm128: a block owns 128 rows of one batch and walks that batch's 128-column tiles of B twice with the t128 K loop (2 x 2 waves of 64 x 64);
+// the scores never leave the registers.  Pass 1 keeps, per lane and row, a running reference accumulator (the row's largest score: max acc for
+// alpha >= 0, min acc for alpha < 0) and the sum l of exp2(c * acc + o), c = alpha * log2(e), o = fl(-float(ref) * c), rescaled by exp2(o_new - o_old)
+// when the reference moves (online softmax); the 8 partials of a row (4 lanes x 2 waves) meet once, in LDS, merged by every lane in the same order.
+// Pass 2 recomputes the products and stores rne(exp2(c * acc + o) * (127 / l)) through a [128 rows][128 B] LDS image as whole row segments.
+// An error of o is common to a row's numerators and its sum and cancels.  With K <= 128 the A tile is loaded once and stays in LDS; the first K step of
+// the next tile is in flight during a tile's epilogue.  CAUSAL: tiles no row of the block can see are skipped in both passes (their B rows are never
+// read) and their outputs zero-filled; only tiles cut by the diagonal or by N take the masked epilogue.
+constexpr int SM_T = 128;
+constexpr float SM_LOG2E = 1.44269502162933349609375f, SM_MAGIC = 12582912.0f;   // 1.5 * 2^23: the low mantissa bits of (x + SM_MAGIC) are rne(x)
+
+template <bool CAUSAL, bool FAST>
+__global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, int8_t *__restrict__ out, int64_t M, int64_t N,
+                                                      int64_t K, int64_t tiles_m, int64_t total, float alpha, bool vec)
+{
+    __shared__ __attribute__((aligned(16))) char lds[3 * SM_T * BMM_TK];   // [A tile | B tile | output image 128 x 128 B, between the passes the rows' partials]
+    char *const xs = lds, *const ws = lds + SM_T * BMM_TK, *const st = lds + 2 * SM_T * BMM_TK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int t16 = lane & 15, q16 = lane >> 4;
+    const int64_t nsteps = (K + BMM_TK - 1) / BMM_TK, shift = N - M;
+    const bool a_once = nsteps == 1, neg = alpha < 0.0f;
+    const float c = alpha * SM_LOG2E;
+    const int ref0 = neg ? INT32_MAX : INT32_MIN;
+
+    for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
+        const int64_t bt = id / tiles_m, m0 = (id - bt * tiles_m) * SM_T;
+        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
+        const int64_t obase = bt * M * N, mlast = (m0 + SM_T < M ? m0 + SM_T : M) - 1;
+        auto visible = [&](int64_t m) -> int64_t {   // keys 0 .. visible(m) - 1 are seen by query m
+            if (!CAUSAL) return N;
+            const int64_t v = m + shift + 1;
+            return v < 0 ? 0 : (v > N ? N : v);
+        };
+        const int64_t n_end = visible(mlast), nt = (n_end + SM_T - 1) / SM_T, nseq = 2 * nt, nfull = visible(m0);
+        int ref[4];
+        float l[4], o[4], inv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ref[i] = ref0, l[i] = 0.0f, o[i] = -(float)ref0 * c, inv[i] = 0.0f;
+        }
+
+        v4i px[4], pw[4];
+        bool pkin = true;
+        // Rows of b from n_end on are never read.  FAST (K % 16 == 0, 16-B aligned operands; its own instantiation) has no branch per lane, so the 8 loads of a K step
+        // are in flight together: a row past the end reads the last valid row instead (A rows >= M are never stored, B rows >= n_end are masked in the
+        // epilogue), a 16-B chunk past K reads chunk 0 and is zeroed on its way into LDS.
+        auto load = [&](int64_t n0, int64_t k0, bool with_a) {
+            const int row = tid >> 3;
+            const int64_t k = k0 + (tid & 7) * 16;
+            if constexpr (FAST) {
+                pkin = k < K;   // applied when the values are written to LDS: nothing here waits for a load
+                const int64_t kc = pkin ? k : 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int64_t ra = m0 + row + 32 * i < M ? m0 + row + 32 * i : M - 1, rb = n0 + row + 32 * i < n_end ? n0 + row + 32 * i : n_end - 1;
+                    if (with_a) px[i] = *(const v4i *)(ab + ra * K + kc);
+                    pw[i] = *(const v4i *)(bb + rb * K + kc);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (with_a) px[i] = load16_guarded(ab, K, m0 + row + 32 * i, M, k, K, false);
+                    pw[i] = load16_guarded(bb, K, n0 + row + 32 * i, n_end, k, K, false);
+                }
+            }
+        };
+        if (FAST && nseq > 0 && nsteps > 0) load(0, 0, true);
+        for (int64_t u = 0; u < nseq; ++u) {
+            const bool second = u >= nt;
+            const int64_t n0 = (second ? u - nt : u) * SM_T;
+            v4i acc[4][4];   // [m tile][n tile] of the wave's 64 x 64
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = (v4i){0, 0, 0, 0};
+            for (int64_t s = 0; s < nsteps; ++s) {
+                if (!FAST) load(n0, s * BMM_TK, !a_once || u == 0);   // (the byte path keeps no loads in flight: registers)
+                __syncthreads();   // the previous step's fragments have been read
+                const bool put_a = !a_once || u == 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int cc = tid + 256 * i, row = cc >> 3, ch = cc & 7;
+                    const int off = row * BMM_TK + ((ch ^ ((row >> 1) & 7)) << 4);
+                    if (put_a) *(v4i *)(xs + off) = pkin ? px[i] : (v4i){0, 0, 0, 0};
+                    *(v4i *)(ws + off) = pkin ? pw[i] : (v4i){0, 0, 0, 0};
+                }
+                __syncthreads();
+                if constexpr (FAST) {
+                    if (s + 1 < nsteps) load(n0, (s + 1) * BMM_TK, true);   // in flight during this step's matrix work ...
+                    else if (u + 1 < nseq) load((u + 1 < nt ? u + 1 : u + 1 - nt) * SM_T, 0, !a_once);   // ... and during the tile's epilogue
+                }
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    const int ch = kk * 4 + q16;
+                    v4i fx[4], fw[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int rx = wm * 64 + i * 16 + t16, rw = wn * 64 + i * 16 + t16;
+                        fx[i] = *(const v4i *)(xs + rx * BMM_TK + ((ch ^ ((rx >> 1) & 7)) << 4));
+                        fw[i] = *(const v4i *)(ws + rw * BMM_TK + ((ch ^ ((rw >> 1) & 7)) << 4));
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[i][j] = MmaI8x16::mma(fw[j], fx[i], acc[i][j]);   // lane: row t16 of m tile i, columns 4 q16 .. + 3 of n tile j
+                }
+            }
+
+            // lane-relative number of visible columns of row i in this tile: element (j, e) is visible iff 16 j + e < lim(i)
+            auto lim = [&](int i) -> int {
+                const int64_t d = visible(m0 + wm * 64 + i * 16 + t16) - n0 - wn * 64 - 4 * q16;
+                return d < 0 ? 0 : (d > 64 ? 64 : (int)d);
+            };
+            auto pass1 = [&](auto masked_) {
+                constexpr bool MASKED = decltype(masked_)::value;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int li = MASKED ? lim(i) : 64;
+                    int tm = ref[i];
+                    if (!neg) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const int v = (!MASKED || 16 * j + e < li) ? acc[i][j][e] : INT32_MIN;
+                                tm = v > tm ? v : tm;
+                            }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const int v = (!MASKED || 16 * j + e < li) ? acc[i][j][e] : INT32_MAX;
+                                tm = v < tm ? v : tm;
+                            }
+                    }
+                    const float on = -(float)tm * c;
+                    float sum = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float ex = __builtin_amdgcn_exp2f(__builtin_fmaf((float)acc[i][j][e], c, on));
+                            sum += (!MASKED || 16 * j + e < li) ? ex : 0.0f;
+                        }
+                    l[i] = l[i] * __builtin_amdgcn_exp2f(on - o[i]) + sum;
+                    ref[i] = tm, o[i] = on;
+                    __builtin_amdgcn_sched_barrier(0);   // one row's 16 chains at a time: interleaving four rows costs registers, not time
+                }
+            };
+            auto pass2 = [&](auto masked_) {
+                constexpr bool MASKED = decltype(masked_)::value;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int li = MASKED ? lim(i) : 64, ir = wm * 64 + i * 16 + t16;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        uint32_t q[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float ex = __builtin_amdgcn_exp2f(__builtin_fmaf((float)acc[i][j][e], c, o[i]));
+                            if (MASKED) ex = 16 * j + e < li ? ex : 0.0f;
+                            q[e] = __float_as_uint(__builtin_fmaf(ex, inv[i], SM_MAGIC));   // low byte: rne(127 p), 0 .. 127
+                        }
+                        const uint32_t pk = __builtin_amdgcn_perm(q[1], q[0], 0x0c0c0400u) | __builtin_amdgcn_perm(q[3], q[2], 0x04000c0cu);
+                        *(uint32_t *)(st + ir * SM_T + (((wn * 4 + j) ^ (ir & 7)) << 4) + 4 * q16) = pk;
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            const bool masked = nfull - n0 < SM_T;   // the block's first row (the shortest) does not see the whole tile
+            if (!second) {
+                if (masked) pass1(std::true_type{});
+                else pass1(std::false_type{});
+                if (u + 1 == nt) {   // the 8 partials of each row meet: [row][wn * 4 + q16] of (o, l), merged in slot order by every lane that owns the row
+                    if (nsteps == 0) __syncthreads();
+                    float2 *const part = (float2 *)st;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) part[(wm * 64 + i * 16 + t16) * 8 + wn * 4 + q16] = make_float2(__int_as_float(ref[i]), l[i]);
+                    __syncthreads();
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float2 *const pr = part + (wm * 64 + i * 16 + t16) * 8;
+                        int r = ref0;
+#pragma unroll
+                        for (int p = 0; p < 8; ++p) {
+                            const int rp = __float_as_int(pr[p].x);
+                            r = neg ? (rp < r ? rp : r) : (rp > r ? rp : r);
+                        }
+                        const float orow = -(float)r * c;
+                        float sum = 0.0f;
+#pragma unroll
+                        for (int p = 0; p < 8; ++p) {
+                            const float lp = pr[p].y;
+                            sum += lp > 0.0f ? lp * __builtin_amdgcn_exp2f(orow - -(float)__float_as_int(pr[p].x) * c) : 0.0f;
+                        }
+                        o[i] = orow;
+                        inv[i] = sum > 0.0f ? 127.0f / sum : 0.0f;   // a row without a visible key is all zeros
+                    }
+                }
+            } else {
+                if (nsteps == 0) __syncthreads();   // (no K loop between two uses of the image)
+                if (masked) pass2(std::true_type{});
+                else pass2(std::false_type{});
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int idx = tid + 256 * i, ir = idx >> 3, ch = idx & 7;
+                    const v4i v = *(const v4i *)(st + ir * SM_T + ((ch ^ (ir & 7)) << 4));
+                    const int64_t m = m0 + ir, n = n0 + ch * 16;
+                    if (m < M && n < N) bmm_store_chunk<1>(out, obase + m * N + n, v, N - n, vec);
+                }
+            }
+        }
+        // columns behind the last visible tile: zeros
+        const int64_t z0 = nt * SM_T;
+        if (CAUSAL && z0 < N) {
+            const int64_t zc = (N - z0 + 15) / 16, rows = mlast - m0 + 1;
+            for (int64_t idx = tid; idx < rows * zc; idx += 256) {
+                const int64_t m = m0 + idx / zc, n = z0 + (idx % zc) * 16;
+                bmm_store_chunk<1>(out, obase + m * N + n, (v4i){0, 0, 0, 0}, N - n, vec);
+            }
+        }
+        __syncthreads();   // the image and the operand tiles are rewritten by the next item of a grid-stride loop
+    }
+}
+
 static inline bool bmm_narrow(int64_t M) { return M <= 16; }
 
 static inline int64_t bmm_grid(int64_t total) { return total < (int64_t(1) << 30) ? total : (int64_t(1) << 30); }
@@ -254,6 +483,20 @@ static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch
     return asq_after_launch(s, "asq_bmm_i8");
 }
 
+static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
+{
+    const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0), vec = (N % 16 == 0) && (((uintptr_t)out & 15) == 0);
+    const int64_t tiles_m = (M + SM_T - 1) / SM_T, total = batch * tiles_m;
+    const dim3 grid((unsigned)bmm_grid(total)), block(256);
+    if (causal && fast) hipLaunchKernelGGL((bmm_i8_sm128<true, true>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
+    else if (causal) hipLaunchKernelGGL((bmm_i8_sm128<true, false>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
+    else if (fast) hipLaunchKernelGGL((bmm_i8_sm128<false, true>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
+    else hipLaunchKernelGGL((bmm_i8_sm128<false, false>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
+    return asq_after_launch(s, "asq_bmm_i8");
+}
+
+static inline bool bmm_softmax_kind(int k) { return k == (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX) || k == (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL); }
+
 static inline bool bmm_mul(int64_t x, int64_t y, int64_t &r) { return !__builtin_mul_overflow(x, y, &r); }
 
 }  // namespace asq
@@ -262,7 +505,9 @@ using namespace asq;
 
 extern "C" const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind)
 {
-    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || out_kind < ASQ_BMM_S32 || out_kind > ASQ_BMM_S8) return "none";
+    if (batch <= 0 || M <= 0 || N <= 0 || K < 0) return "none";
+    if (bmm_softmax_kind(out_kind)) return "sm128";
+    if (out_kind < ASQ_BMM_S32 || out_kind > ASQ_BMM_S8) return "none";
     return bmm_narrow(M) ? "m16" : "t128";
 }
 
@@ -275,12 +520,13 @@ extern "C" int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_k
     ASQ_REQUIRE(bmm_mul(M, N, mn) && bmm_mul(batch, mn, bmn) && bmm_mul(bmn, 4, bytes) && bmm_mul(M, K, mk) && bmm_mul(batch, mk, bmk) && bmm_mul(N, K, nk) &&
                     bmm_mul(batch, nk, bnk),
                 ASQ_ERR_DIM, "asq_bmm_i8: size overflows 64 bits (batch=%lld M=%lld N=%lld K=%lld)", (long long)batch, (long long)M, (long long)N, (long long)K);
-    ASQ_REQUIRE(out_kind == ASQ_BMM_S32 || out_kind == ASQ_BMM_F32 || out_kind == ASQ_BMM_S8, ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
+    ASQ_REQUIRE(out_kind == ASQ_BMM_S32 || out_kind == ASQ_BMM_F32 || out_kind == ASQ_BMM_S8 || bmm_softmax_kind(out_kind), ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
     if (bmn == 0) return ASQ_OK;
     ASQ_REQUIRE(out != nullptr, ASQ_ERR_NULL, "asq_bmm_i8: NULL out");
     ASQ_REQUIRE(K == 0 || (a != nullptr && b != nullptr), ASQ_ERR_NULL, "asq_bmm_i8: NULL a / b");
-    ASQ_REQUIRE(out_kind == ASQ_BMM_S8 || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
+    ASQ_REQUIRE(out_kind == ASQ_BMM_S8 || bmm_softmax_kind(out_kind) || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
     hipStream_t s = (hipStream_t)stream;
+    if (bmm_softmax_kind(out_kind)) return launch_bmm_softmax(a, b, (int8_t *)out, batch, M, N, K, alpha, (out_kind & ASQ_BMM_CAUSAL) != 0, s);
     switch (out_kind) {
     case ASQ_BMM_S32: return launch_bmm<ASQ_BMM_S32>(a, b, out, batch, M, N, K, alpha, s);
     case ASQ_BMM_F32: return launch_bmm<ASQ_BMM_F32>(a, b, out, batch, M, N, K, alpha, s);

@@ -1,4 +1,5 @@
 """Functional batched int8 matmuls (reference autosmoothquant/layers/functional/bmm.py)."""
+from ... import ops
 from ..._CUDA import bmm_s8t_s8n_s8t, bmm_s8t_s8n_s32t
 
 
@@ -10,3 +11,8 @@ def bmm_i8_o8(a, b, scale):
 def bmm_i8_o32(a, b):
     # a: [B, M, K] int8, b: [B, N, K] int8 -> [B, M, N] int32 = a . b^T
     return bmm_s8t_s8n_s32t(a, b)
+
+
+def bmm_i8_softmax_o8(a, b, scale, causal=False):
+    # a: [B, M, K] int8, b: [B, N, K] int8, scale: float -> [B, M, N] int8 = rne(127 * softmax(scale * (a . b^T), -1)), one launch
+    return ops.bmm_i8_softmax_q8(a, b, scale, causal)

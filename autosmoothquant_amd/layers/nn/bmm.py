@@ -6,10 +6,13 @@
 
 Checkpoint contract (as the reference): BMM_S8T_S8N_S8T and BMM_S8T_S8N_F32T hold one buffer ``a`` (the scalar alpha,
 a 0-dim tensor whose dtype follows the module's, so ``.half()`` rounds it to fp16); BMM_S8T_S8N_S32T holds none.
+BMM_S8T_S8N_SOFTMAX_S8T (not in the reference: QK^T with the softmax -> int8 epilogue fused, the P that BMM_S8T_S8N_S8T
+consumes) holds ``a`` as its siblings; ``causal`` is a plain attribute and not part of the state dict.
 ``a`` lives on the HOST after any ``.cuda()/.to()``, so ``forward`` reads it without synchronising the device; the
 kernel receives fp32(a.item()), which is the reference's ``float alpha`` argument."""
 import torch
 
+from ... import ops
 from ..._CUDA import bmm_s8t_s8n_s8t, bmm_s8t_s8n_s32t, bmm_s8t_s8n_f32t
 
 
@@ -62,6 +65,22 @@ class BMM_S8T_S8N_F32T(_ScaledBMM):
     @staticmethod
     def from_scale(a_scale, b_scale):
         return BMM_S8T_S8N_F32T._with_alpha(a_scale * b_scale)
+
+
+class BMM_S8T_S8N_SOFTMAX_S8T(_ScaledBMM):
+    def __init__(self, alpha, causal=False):
+        super().__init__(alpha)
+        self.causal = bool(causal)
+
+    def forward(self, a, b):
+        # a: [B, M, K] int8, b: [B, N, K] int8 -> [B, M, N] int8 = rne(127 * softmax(alpha * (a . b^T), -1)); causal: n <= m + (N - M)
+        return ops.bmm_i8_softmax_q8(a, b, self._alpha(), self.causal)
+
+    @staticmethod
+    def from_scale(a_scale, b_scale, causal=False):
+        mod = BMM_S8T_S8N_SOFTMAX_S8T._with_alpha(a_scale * b_scale)
+        mod.causal = bool(causal)
+        return mod
 
 
 class BMM_S8T_S8N_S32T(torch.nn.Module):

@@ -962,6 +962,25 @@ def bmm_i8(a, b, out_kind, alpha=1.0):
     return out
 
 
+def bmm_i8_softmax_q8(a, b, alpha, causal=False):
+    """QK^T with the softmax -> int8 epilogue fused (asq_bmm_i8 with ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]): a int8 [B, M, K], b int8 [B, N, K]
+    -> a new int8 [B, M, N] = rne(127 * softmax(alpha * (a . b^T), -1)) on the current stream, values 0 .. 127; the fp32 scores never reach memory.
+    causal: key n is visible to query m iff n <= m + (N - M); invisible elements are 0.  alpha reaches the kernel as fp32."""
+    _dev(a, "a"), _dev(b, "b")
+    if a.dtype != torch.int8 or b.dtype != torch.int8:
+        raise RuntimeError(f"expected int8 a and b, got {a.dtype} and {b.dtype}")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
+        raise ValueError(f"shape mismatch: a {tuple(a.shape)} must be [B, M, K] and b {tuple(b.shape)} [B, N, K]")
+    dev = _same_device(a, b)
+    B, M, K = a.shape
+    N = b.shape[1]
+    kind = L.ASQ_BMM_S8 | L.ASQ_BMM_SOFTMAX | (L.ASQ_BMM_CAUSAL if causal else 0)
+    out = torch.empty((B, M, N), dtype=torch.int8, device=dev)
+    with _on(dev):
+        L.check(L.lib().asq_bmm_i8(a.data_ptr(), b.data_ptr(), out.data_ptr(), kind, B, M, N, K, float(alpha), _stream(a)), "asq_bmm_i8")
+    return out
+
+
 def bmm_kernel_name(batch, M, N, K, out_kind=L.ASQ_BMM_F32):
     return L.lib().asq_bmm_kernel_name(batch, M, N, K, _BMM_KIND.get(out_kind, out_kind) if isinstance(out_kind, torch.dtype) else out_kind).decode()
 

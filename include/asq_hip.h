@@ -394,10 +394,29 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
  * reference needs K % 16 == 0; K % 16 == 0 with 16-B aligned operands takes the unguarded load path); K = 0 writes alpha * 0.0 (S32: 0).
  * ASQ_ERR_DIM: a negative size or batch * M * N (x 4 bytes), batch * M * K, batch * N * K overflowing 64 bits;  ASQ_ERR_DTYPE: unknown out_kind;
  * ASQ_ERR_NULL: out NULL on a non-empty output, a / b NULL with K > 0;  ASQ_ERR_ALIGN: out not aligned to its element.  An empty output is a no-op.
- * No workspace.  asq_bmm_kernel_name: "m16" (M <= 16: one 16-row tile, B streamed into the matrix cores), "t128" (128 x 128 tiles), "none" (empty / invalid). */
+ * No workspace.  asq_bmm_kernel_name: "m16" (M <= 16: one 16-row tile, B streamed into the matrix cores), "t128" (128 x 128 tiles), "sm128" (the softmax kinds, below), "none" (empty / invalid). */
 #define ASQ_BMM_S32 0 /* bmm_s8t_s8n_s32t: out int32 = acc (alpha ignored)           */
 #define ASQ_BMM_F32 1 /* bmm_s8t_s8n_f32t: out float = alpha * float(acc)            */
 #define ASQ_BMM_S8 2  /* bmm_s8t_s8n_s8t : out int8  = sat_i8(rne(alpha*float(acc))) */
+/* out_kind is a base kind in the low bits plus flags.  The valid values are 0, 1, 2, ASQ_BMM_S8 | ASQ_BMM_SOFTMAX (18) and
+ * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50); every other value is ASQ_ERR_DTYPE / "none".
+ *
+ * The softmax kinds turn QK^T into the int8 probabilities that P.V consumes (asq_bmm_i8(p, vT, ASQ_BMM_S8) with alpha = v_scale / (127 * out_scale))
+ * without the fp32 scores ever reaching memory.  out is int8 [batch, M, N]; per batch i and row m
+ *   acc[m, n] = sum_k a[i, m, k] * b[i, n, k]                  exact int32, as every other kind
+ *   s[m, n]   = alpha * float(acc[m, n])                       the ASQ_BMM_F32 value
+ *   vis(m, n) = !causal || n <= m + (N - M)                    bottom-right aligned: decode (M = 1) sees every key
+ *   p[m, n]   = exp(s[m, n] - max_vis s[m, :]) / sum_vis exp(s[m, :] - max)     over the visible n
+ *   out[m, n] = int8(rne(127 * p[m, n])) for visible n, 0 otherwise              values 0 .. 127
+ * A row without a visible key (causal, M > N, m < M - N) is all zeros; K = 0 gives p = 1 / (number of visible keys).  alpha may be negative or zero and
+ * must be finite (otherwise the result is unspecified, but only out is written).  p is evaluated in fp32 through exp2 with log2(e) folded into alpha and
+ * an online (tile by tile) sum: it is within 2^-11 relative (N <= 4096; N * 2^-23 beyond) of the float64 value for |s| < 2^10, so out differs from the
+ * correctly rounded value only where 127 p lies that close to a rounding tie, and then by 1.  Deterministic: a fixed reduction order, no atomics; a batch
+ * entry's bytes do not depend on batch or on its index.  Argument rules, error order, alignment freedom and the no-workspace rule are those of ASQ_BMM_S8.
+ * asq_bmm_kernel_name answers "sm128" for them (a block owns 128 rows of a batch and walks B twice: online row maximum and sum, then recompute and
+ * store).  There is no version bump for these kinds: probe with asq_bmm_kernel_name(batch, M, N, K, 18) != "none"; an older library answers "none". */
+#define ASQ_BMM_SOFTMAX 0x10 /* with ASQ_BMM_S8 only: row softmax of alpha * acc, then int8(rne(127 p)) */
+#define ASQ_BMM_CAUSAL 0x20  /* with ASQ_BMM_SOFTMAX only: key n is visible to query m iff n <= m + (N - M) */
 int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind,
                int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream);
 const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind);
