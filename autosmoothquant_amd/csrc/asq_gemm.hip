@@ -1,4 +1,4 @@
-// C-ABI entry points of the INT8 GEMM family (kernels: asq_gemm_kernels.h, asq_gemm_p8.h;
+// C-ABI entry points of the INT8 GEMM family (kernels: asq_gemm_kernels.h, asq_gemm_p8.h; launch plan: asq_gemm_plan.h;
 // fp epilogue instantiations: asq_gemm_inst_{f32,f16,bf16}.hip).
 #include "asq_gemm_kernels.h"
 
@@ -38,11 +38,12 @@ static int check_gemm_args(const char *what, const void *x, const void *w, const
 
 using namespace asq;
 
+// The queries read the plan of an aligned call with unlimited scratch, for "any epilogue" (EPI_CAPS_ANY, asq_gemm_plan.h).
 extern "C" const char *asq_gemm_kernel_name(int64_t M, int64_t N, int64_t K)
 {
-    const GemmKernel kern = pick_kernel(nullptr, nullptr, M, N, K);
-    if (plan_tail_peel(kern, M, N, K).n_main > 0) return kern == KERN_P8 ? "p8+tail" : kern == KERN_P8H ? "p8h+tail" : kern == KERN_P16 ? "p16+tail" : "p4+tail";
-    switch (kern) {
+    const GemmPlan g = plan_gemm(EPI_CAPS_ANY, plan_query(M, N, K));
+    if (g.nparts == 2) return g.cls == KERN_P8 ? "p8+tail" : g.cls == KERN_P8H ? "p8h+tail" : g.cls == KERN_P16 ? "p16+tail" : "p4+tail";
+    switch (g.cls) {
     case KERN_P8: return "p8";
     case KERN_P8H: return "p8h";
     case KERN_P4: return "p4";
@@ -54,28 +55,14 @@ extern "C" const char *asq_gemm_kernel_name(int64_t M, int64_t N, int64_t K)
     }
 }
 
+// What the launches of the plan can use behind the header: split-K slabs or register images (the larger of a 128 x 128 split's two forms; for a tail peel the
+// remainder's -- a launch with >= 256 tiles never splits K as a whole), the stream-K kernel's partial tiles.
 extern "C" size_t asq_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K)
 {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const GemmKernel kern = pick_kernel(nullptr, nullptr, M, N, K);
+    const GemmPlan g = plan_gemm(EPI_CAPS_ANY, plan_query(M, N, K));
     size_t scratch = 0;
-    const TailPeel tp = plan_tail_peel(kern, M, N, K);
-    if (tp.n_main > 0) {
-        scratch = tp.ws_bytes;  // (a launch with >= 256 tiles never splits K as a whole; its peeled remainder may)
-    } else if (kern == KERN_SKINNY) {
-        scratch = plan_wstream(M, N, K).bytes;  // partial slabs of the in-launch reduction (asq_gemm_wstream.h)
-    } else if (kern == KERN_P8 || kern == KERN_P8H || kern == KERN_P8Q) {
-        const int s = kern == KERN_P8    ? pick_ksplit(((M + 255) / 256) * ((N + 255) / 256), K, M, N, (size_t)-1)
-                      : kern == KERN_P8H ? pick_ksplit_p8h(((M + 127) / 128) * ((N + 255) / 256), K, M, N, (size_t)-1)
-                                         : pick_ksplit_p8q(((M + 127) / 128) * ((N + 127) / 128), K, M, N, (size_t)-1);
-        scratch = s > 1 ? (size_t)s * (size_t)M * (size_t)N * 4 : 0;
-        if (kern == KERN_P8Q) {   // the in-launch reduction of gemm_i8_p8q2<Epi, true> keeps one 64 KiB register image per (tile, split): whole tiles, and its own split count
-            const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128);
-            const int sf = tiles <= WS_MAX_GROUPS ? pick_ksplit_p8q(tiles, K, M, N, (size_t)-1, true) : 1;
-            const size_t fb = sf > 1 ? p8q_fix_bytes(tiles, sf) : 0;
-            scratch = fb > scratch ? fb : scratch;
-        }
-    }
+    for (int i = 0; i < g.nparts; ++i) scratch = g.part[i].scratch > scratch ? g.part[i].scratch : scratch;
     return scratch ? scratch + WS_HEADER_BYTES : 0;
 }
 
@@ -147,12 +134,12 @@ extern "C" int asq_offsets_supported(int64_t M, int64_t N, int64_t K, int out_dt
 {
     if (!offsets_enabled() || (out_dtype != ASQ_F16 && out_dtype != ASQ_BF16 && out_dtype != ASQ_F32) || M <= 0 || N <= 0 || K <= 0) return 0;
     if (!offsets_shape_ok(nullptr, nullptr, M, N, K) || K / (out_dtype == ASQ_F32 ? 4 : 8) > 256 * 20) return 0;   // (second: asq_quantize_act_off keeps the row in registers)
-    const GemmKernel kern = pick_kernel(nullptr, nullptr, M, N, K);
-    if (kern != KERN_P16) return 0;
+    const GemmPlan g = plan_gemm(EPI_CAPS_ANY, plan_query(M, N, K));
+    if (g.cls != KERN_P16) return 0;
     // a launch with a peeled column remainder runs on plain operands (the remainder kernels take no images) -- unless it has three or more full rounds: then the
     // images are worth more than the peel (8192 x 11008 x 4096: -5.7 % against -3.2 %; 2048 x 11008 x 4096: -2.7 % against -9.5 %; profiles/r4_tail_rule_ab.txt)
     const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
-    return plan_tail_peel(kern, M, N, K).n_main == 0 || tiles >= 3 * 256 ? 1 : 0;
+    return g.nparts == 1 || tiles >= 3 * 256 ? 1 : 0;
 }
 
 extern "C" int asq_linear_w8a8_off(const int8_t *xq_off, const int8_t *w_off, void *out, int out_dtype, int64_t M, int64_t N, int64_t K, float s_scalar,

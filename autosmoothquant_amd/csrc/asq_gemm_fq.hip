@@ -19,7 +19,8 @@ static bool fused_shape(const void *x, const void *w, int64_t M, int64_t N, int6
     if (!fused_enabled() || forced_kernel() >= 0) return false;
     if (!skfq_supported(x, w, M, N, K, x_dtype, act_mode)) return false;
     // only where the dispatcher streams the weight anyway (gemm_i8_skinny's region, outside the stream-K kernel's: those are long-K shapes whose X image would not fit)
-    return pick_kernel(x, w, M, N, K) == KERN_SKINNY && plan_wstream(M, N, K).G == 0;
+    const LaunchPlan p = plan_gemm(EPI_CAPS_ANY, plan_query(M, N, K, ((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0)).part[0];
+    return p.kern == KERN_SKINNY && p.ws.G == 0;
 }
 
 extern "C" int asq_forward_fused_supported(int64_t M, int64_t N, int64_t K, int x_dtype, int act_mode)

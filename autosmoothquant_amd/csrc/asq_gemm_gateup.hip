@@ -14,41 +14,19 @@ static bool gate_up_shape(int64_t M, int64_t F, int64_t K, int out_dtype)
 
 extern "C" int asq_gate_up_supported(int64_t M, int64_t F, int64_t K, int out_dtype) { return gate_up_shape(M, F, K, out_dtype) ? 1 : 0; }
 
-template <int DT, bool ROW>
-static int launch_gate_up(const int8_t *xq, const int8_t *w_gu, void *out, int64_t M, int64_t F, int64_t K, float s_gate, float s_up, const float *s_row, int fast,
-                          OffsetArgs off, hipStream_t s)
+// one launch of the persistent 256 x 256 kernel over [M, 2 F] with the caller's EpiGateUp (2-byte outputs or int8 quantised ones)
+template <class Epi>
+static int launch_gate_up(const int8_t *xq, const int8_t *w_gu, int64_t M, int64_t F, int64_t K, const Epi &epi, OffsetArgs off, hipStream_t s, const char *what)
 {
-    using Epi = EpiGateUp<DT, ROW>;
     auto kfn = gemm_i8_p16p<Epi>;
     const hipError_t e = ensure_dynamic_lds((const void *)kfn, P16P_LDS_BYTES);
     if (e != hipSuccess) {
-        asq_set_error("asq_linear_w8a8_gate_up: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
         return (int)e;
     }
-    const int64_t N = 2 * F, tm = M / 256, tn = N / 256, T = tm * tn;
-    const int64_t grid = T < 8 * P8_CUS_PER_XCD ? T : 8 * P8_CUS_PER_XCD;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), P16P_LDS_BYTES, s, xq, w_gu, M, N, K, (int)tm, (int)tn, Epi{out, F, s_row, s_gate, s_up, 1.0f, fast}, off);
-    return asq_after_launch(s, "asq_linear_w8a8_gate_up");
-}
-
-template <int DT, bool ROW>
-static int launch_gate_up_q8(const int8_t *xq, const int8_t *w_gu, int8_t *out, int64_t M, int64_t F, int64_t K, float s_gate, float s_up, const float *s_row, int fast, float qs,
-                             OffsetArgs off, hipStream_t s)
-{
-    using Epi = EpiGateUp<DT, ROW, true>;
-    auto kfn = gemm_i8_p16p<Epi>;
-    const hipError_t e = ensure_dynamic_lds((const void *)kfn, P16P_LDS_BYTES);
-    if (e != hipSuccess) {
-        asq_set_error("asq_linear_w8a8_gate_up_q8: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    const int64_t N = 2 * F, tm = M / 256, tn = N / 256, T = tm * tn;
-    const int64_t grid = T < 8 * P8_CUS_PER_XCD ? T : 8 * P8_CUS_PER_XCD;
-    Epi epi{out, F, s_row, s_gate, s_up, 1.0f, fast};
-    epi.qs = qs;
-    epi.qy = (qs > 0x1p-60f && qs < 0x1p60f) ? 1.0f / qs : 0.0f;   // (asq_quantize_act's own choice between the two divisions: the same int8 either way)
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), P16P_LDS_BYTES, s, xq, w_gu, M, N, K, (int)tm, (int)tn, epi, off);
-    return asq_after_launch(s, "asq_linear_w8a8_gate_up_q8");
+    const int64_t N = 2 * F, tm = M / 256, tn = N / 256;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)persistent_grid(tm * tn)), dim3(512), P16P_LDS_BYTES, s, xq, w_gu, M, N, K, (int)tm, (int)tn, epi, off);
+    return asq_after_launch(s, what);
 }
 
 extern "C" int asq_linear_w8a8_gate_up_q8(const int8_t *xq, const int8_t *w_gu, int8_t *out_q, int act_dtype, int64_t M, int64_t F, int64_t K, float s_gate, float s_up,
@@ -69,8 +47,13 @@ extern "C" int asq_linear_w8a8_gate_up_q8(const int8_t *xq, const int8_t *w_gu, 
     const OffsetArgs off{row_off, col_off};
     const int fast = (flags & ASQ_SILU_FAST) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    if (act_dtype == ASQ_F16) return s_row ? launch_gate_up_q8<ASQ_F16, true>(xq, w_gu, out_q, M, F, K, s_gate, s_up, s_row, fast, quant_scale, off, s) : launch_gate_up_q8<ASQ_F16, false>(xq, w_gu, out_q, M, F, K, s_gate, s_up, s_row, fast, quant_scale, off, s);
-    return s_row ? launch_gate_up_q8<ASQ_BF16, true>(xq, w_gu, out_q, M, F, K, s_gate, s_up, s_row, fast, quant_scale, off, s) : launch_gate_up_q8<ASQ_BF16, false>(xq, w_gu, out_q, M, F, K, s_gate, s_up, s_row, fast, quant_scale, off, s);
+    auto go = [&](auto epi) {
+        epi.qs = quant_scale;
+        epi.qy = (quant_scale > 0x1p-60f && quant_scale < 0x1p60f) ? 1.0f / quant_scale : 0.0f;   // (asq_quantize_act's own choice between the two divisions: the same int8 either way)
+        return launch_gate_up(xq, w_gu, M, F, K, epi, off, s, "asq_linear_w8a8_gate_up_q8");
+    };
+    if (act_dtype == ASQ_F16) return s_row ? go(EpiGateUp<ASQ_F16, true, true>{out_q, F, s_row, s_gate, s_up, 1.0f, fast}) : go(EpiGateUp<ASQ_F16, false, true>{out_q, F, s_row, s_gate, s_up, 1.0f, fast});
+    return s_row ? go(EpiGateUp<ASQ_BF16, true, true>{out_q, F, s_row, s_gate, s_up, 1.0f, fast}) : go(EpiGateUp<ASQ_BF16, false, true>{out_q, F, s_row, s_gate, s_up, 1.0f, fast});
 }
 
 extern "C" int asq_linear_w8a8_gate_up(const int8_t *xq, const int8_t *w_gu, void *out, int out_dtype, int64_t M, int64_t F, int64_t K, float s_gate, float s_up,
@@ -90,8 +73,8 @@ extern "C" int asq_linear_w8a8_gate_up(const int8_t *xq, const int8_t *w_gu, voi
     const OffsetArgs off{row_off, col_off};
     const int fast = (flags & ASQ_SILU_FAST) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    if (out_dtype == ASQ_F16) return s_row ? launch_gate_up<ASQ_F16, true>(xq, w_gu, out, M, F, K, s_gate, s_up, s_row, fast, off, s) : launch_gate_up<ASQ_F16, false>(xq, w_gu, out, M, F, K, s_gate, s_up, s_row, fast, off, s);
-    return s_row ? launch_gate_up<ASQ_BF16, true>(xq, w_gu, out, M, F, K, s_gate, s_up, s_row, fast, off, s) : launch_gate_up<ASQ_BF16, false>(xq, w_gu, out, M, F, K, s_gate, s_up, s_row, fast, off, s);
+    if (out_dtype == ASQ_F16) return s_row ? launch_gate_up(xq, w_gu, M, F, K, EpiGateUp<ASQ_F16, true>{out, F, s_row, s_gate, s_up, 1.0f, fast}, off, s, "asq_linear_w8a8_gate_up") : launch_gate_up(xq, w_gu, M, F, K, EpiGateUp<ASQ_F16, false>{out, F, s_row, s_gate, s_up, 1.0f, fast}, off, s, "asq_linear_w8a8_gate_up");
+    return s_row ? launch_gate_up(xq, w_gu, M, F, K, EpiGateUp<ASQ_BF16, true>{out, F, s_row, s_gate, s_up, 1.0f, fast}, off, s, "asq_linear_w8a8_gate_up") : launch_gate_up(xq, w_gu, M, F, K, EpiGateUp<ASQ_BF16, false>{out, F, s_row, s_gate, s_up, 1.0f, fast}, off, s, "asq_linear_w8a8_gate_up");
 }
 
 // ---- grouped form (round 5, last session): Mixtral's w1 || w3 (reference models/mixtral.py:99-101,142-145: w2(act(w1 x) * w3 x) per expert) as ONE grouped launch of the
@@ -112,13 +95,9 @@ static int launch_grouped_gate_up(const int8_t *xq, const int8_t *w_gu, void *ou
 {
     using Epi = EpiGateUp<DT, false>;
     const int64_t N = 2 * F, tn = N / 256;
-    int64_t tiles = (M / 256 + ngroups) * tn;   // upper bound on sum ceil(m_g / 256) * tn (launch_gemm_impl's grouped branch)
-    char *gws = nullptr;
-    if (ngroups <= P8_GROUPED_SCAN_MAX) {
-        tiles = 8 * ((tiles + 7) / 8 + 2 + P8_CUS_PER_XCD);
-        if (ws != nullptr && ws_bytes >= (size_t)WS_HEADER_BYTES + P8_GROUPED_WS_BYTES && grouped_tail_split_enabled()) gws = (char *)ws;
-    }
-    ASQ_REQUIRE(tiles < (1ll << 24), ASQ_ERR_DIM, "asq_linear_w8a8_grouped_gate_up: too many tiles");
+    const bool has_header = ws != nullptr && ws_bytes >= (size_t)WS_HEADER_BYTES;
+    const GroupedGrid gg = grouped_grid(M, N, ngroups, true, has_header, has_header ? ws_bytes - WS_HEADER_BYTES : 0);
+    ASQ_REQUIRE(gg.tiles < (1ll << 24), ASQ_ERR_DIM, "asq_linear_w8a8_grouped_gate_up: too many tiles");
     auto kfn = gemm_i8_p8<Epi, 0, true, true>;
     const bool g_offs = off.row != nullptr;
     const int lds = g_offs ? P16_LDS_BYTES : P8_LDS_BYTES;
@@ -130,7 +109,7 @@ static int launch_grouped_gate_up(const int8_t *xq, const int8_t *w_gu, void *ou
     Epi epi{out, F, nullptr, 1.0f, 1.0f, 1.0f, fast};
     epi.sg_group = s_gate;
     epi.su_group = s_up;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)tiles), dim3(512), lds, s, xq, w_gu, M, N, K, 0, (int)tn, 1, goffs, ngroups, gws, epi, g_offs ? off : OffsetArgs{});
+    hipLaunchKernelGGL(kfn, dim3((unsigned)gg.tiles), dim3(512), lds, s, xq, w_gu, M, N, K, 0, (int)tn, 1, goffs, ngroups, gg.tail_split ? (char *)ws : nullptr, epi, g_offs ? off : OffsetArgs{});
     return asq_after_launch(s, "asq_linear_w8a8_grouped_gate_up");
 }
 
@@ -176,8 +155,7 @@ static int launch_fp8_grouped_gate_up(const int8_t *xq, const int8_t *w_gu, void
 {
     using Epi = EpiGateUpFp8<DT>;
     const int64_t N = 2 * F, tn = N / 256;
-    int64_t tiles = (M / 256 + ngroups) * tn;   // upper bound on sum ceil(m_g / 256) * tn
-    if (ngroups <= P8_GROUPED_SCAN_MAX) tiles = 8 * ((tiles + 7) / 8 + 2 + P8_CUS_PER_XCD);
+    const int64_t tiles = grouped_grid(M, N, ngroups, false, false, 0).tiles;
     ASQ_REQUIRE(tiles < (1ll << 24), ASQ_ERR_DIM, "asq_linear_fp8_grouped_gate_up: too many tiles");
     auto kfn = gemm_i8_p8<Epi, 0, true, false>;
     const hipError_t e = ensure_dynamic_lds((const void *)kfn, P8_LDS_BYTES);

@@ -24,6 +24,7 @@
 //      stores on their write acknowledgements -- measured 2.7x on the whole epilogue).
 #pragma once
 #include "asq_common.h"
+#include "asq_gemm_plan.h"
 #include <string.h>
 #include <type_traits>
 #include <utility>
@@ -1003,10 +1004,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg)
     return base + slot;
 }
 
-// workspace header (asq_workspace_init): magic word + arrival tickets of the in-launch reductions (asq_gemm_wstream.h; grouped tail split of asq_gemm_p8.h)
-constexpr int WS_HEADER_BYTES = 8192;
+// workspace header (WS_HEADER_BYTES, WS_MAX_GROUPS: asq_gemm_plan.h): its magic word
 constexpr unsigned long long WS_MAGIC = 0x4153515753763031ull;  // "ASQWSv01"
-constexpr int WS_MAX_GROUPS = (WS_HEADER_BYTES - 16) / 4;
 
 // OFFSET operands (asq_linear_w8a8_off; include/asq_hip.h "offset operand images").  Under the socket power limit the 256 x 256 GEMM's time is its
 // energy, and most of the matrix cores' data-dependent energy is two's-complement sign extension (profiles/r2_clock_power_evidence.md section 3,
@@ -1020,7 +1019,7 @@ struct OffsetArgs {
     const int32_t *row = nullptr;  // [M][2]: {cx[m], sum_k x'[m,k]}       (written by the activation quantiser, asq_quantize_act_off)
     const int32_t *col = nullptr;  // [N][2]: {cw[n], sum_k w[n,k]}        (sum of the ORIGINAL weight row; asq_weight_offset_image)
 };
-constexpr int64_t OFFSET_MAX_K = 65536;   // the start values are formed with 24-bit multiplies: |sum_k| <= 128 K < 2^23 + 1
+// (K <= OFFSET_MAX_K, asq_gemm_plan.h: the start values are formed with 24-bit multiplies, |sum_k| <= 128 K < 2^23 + 1)
 
 // epilogues of the gate || up GEMMs (asq_gemm_gateup.h) mark themselves with kGateUp; the kernels that carry them select their epilogue on this trait
 template <class Epi, class = void> struct IsGateUp : std::false_type {};
@@ -1102,12 +1101,6 @@ __device__ __forceinline__ bool splitk_fix_reduce(char *gws, unsigned long long 
 #include "asq_gemm_p8.h"
 #include "asq_gemm_p4.h"
 #include "asq_gemm_p16.h"
-#ifndef ASQ_P16_TAIL
-#define ASQ_P16_TAIL 0   // 1: also build gemm_i8_p16t (asq_gemm_p16t.h: round 6, bit-identical to gemm_i8_p16 and no faster -- not shipped) and dispatch it
-#endif
-#if ASQ_P16_TAIL
-#include "asq_gemm_p16t.h"
-#endif
 #include "asq_gemm_gateup.h"
 #include "asq_gemm_p16p.h"
 #include "asq_gemm_p4x16.h"
@@ -1157,183 +1150,13 @@ __global__ void __launch_bounds__(256) splitk_reduce(const int32_t *__restrict__
 }
 
 // ---------------------------------------------------------------------------------
-// dispatch + launch
+// launch: plan_gemm() (asq_gemm_plan.h) decides, launch_gemm_impl() executes
 // ---------------------------------------------------------------------------------
-enum GemmKernel { KERN_GENERIC = 0, KERN_SKINNY = 1, KERN_P8 = 2, KERN_P8H = 3, KERN_P4 = 4, KERN_P8Q = 5, KERN_P16 = 6, KERN_P4X16 = 7 };
-
-// ASQ_P8Q2=0: the 128 x 128 int8 launches stay on gemm_i8_p8q (one barrier per K-tile) instead of gemm_i8_p8q2 (two staggered wave groups); A/B switch, read once
-static inline int p8q2_enabled()   // 0: gemm_i8_p8q; 1: gemm_i8_p8q2
-{
-    static const int on = [] {
-        const char *e = getenv("ASQ_P8Q2");
-        return e ? atoi(e) : 1;
-    }();
-    return on;
-}
-
-int forced_kernel();  // env ASQ_GEMM_KERNEL=generic|skinny|p8|p8h (development / A-B aid), asq_gemm.hip
-
-static inline GemmKernel pick_kernel(const void *x, const void *w, int64_t M, int64_t N, int64_t K)
-{
-    const bool aligned = ((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0;
-    const bool tiled_ok = aligned && K % 128 == 0 && K >= 128 && K <= (1 << 24);
-    const int f = forced_kernel();
-    if (f == KERN_GENERIC) return KERN_GENERIC;
-    if (tiled_ok && (f == KERN_P8 || f == KERN_P8H || f == KERN_P4 || f == KERN_P8Q || f == KERN_P16 || f == KERN_P4X16)) return (GemmKernel)f;
-    if (tiled_ok && M <= 1024 && M * K < (1ll << 32) && f == KERN_SKINNY) return KERN_SKINNY;  // (32-bit row offsets in the DMA address)
-    if (tiled_ok && f < 0) {
-        // measured crossover (tools/cold_grid.sh: 48..256 rows x 8 LLaMA/OPT/Mixtral weight shapes, weights rotated
-        // through > 256 MiB so they come from HBM, not the Infinity Cache): the weight-streaming kernel re-reads X
-        // from L2 once per 16 (or 32) channels, so it wins while the total work N*K*M stays small; wide-N
-        // weights (11008x4096, 14336x4096, 20480x5120) stay ahead longer than square or long-K ones
-        const double work = (double)N * (double)K * (double)M;
-        const int64_t th = ((M + 127) / 128) * ((N + 255) / 256);  // tiles of 128 x 256
-        // (against the 128 x 128 kernel the square-ish crossover sits lower once there are more than 64 rows: 96x5120x5120 17.1 -> 14.5 us,
-        // 128x5120x5120 19.5 -> 15.5, while 128x4096x4096 stays with the stream, 11.7 vs 15.0)
-        if (M <= 256 && work <= (N > 2 * K ? 5.8e9 : M > 64 ? 2.4e9 : 4.0e9) && !(M > 160 && th >= 16))
-            return KERN_SKINNY;  // (measured up to 256 rows; with more than 160 rows the 128 x 128 kernel is 5-10 % ahead once it has >= 32 tiles)
-        // 128-row tiles when the 256-row tiling cannot fill 256 CUs (or wastes half a tile row).  Measured
-        // (tools/ksplit_sweep.sh): p8h is ~14 % slower per op on a full chip but wins up to 1.45x below ~144 tiles
-        const int64_t t256 = ((M + 255) / 256) * ((N + 255) / 256);
-        // two one-round corners (round 4, profiles/r4_dispatch_holes.txt, forced kernels on cold weights): 129..143 tiles of 256 x 256 whose 128 x 256 tiling no
-        // longer fits ONE round run faster as one (partly filled) round of p16 than as p8h + a peeled remainder (768 x 11008 x 4096: 40.4 -> 37.3 us); and
-        // >= 144 tiles whose last 256-row tile row is at most half full while the 128 x 256 tiling fits one round stay with p8h (640 x 12288 x 4096: 37.5 -> 28.6)
-        const bool one_round_p16 = t256 >= 128 && th > 256;
-        const bool odd_half_row = t256 >= 144 && th <= 256 && (((M + 127) / 128) & 1) != 0 && K < 16384;
-        if ((t256 < 144 && !one_round_p16) || odd_half_row) {
-            if (odd_half_row) return KERN_P8H;
-            // 128 x 128 tiles (p8q) where the 128 x 256 tiling has at most 128 tiles, i.e. leaves half of the CUs without one: twice the
-            // tiles at twice the L2->LDS bytes per MFMA.  Measured (tools/kbench.py, forced vs default, 48 shapes): -3 ... -22 % for 32..128
-            // p8h tiles (512 x 4096 x 4096: 22.8 -> 17.7 us), +15 ... +35 % above 128.
-            // (with its cost-model K split p8q also wins 5-13 % at 16..32 tiles and a long K -- 128x4096x11008 20.4 -> 19.0 us; between 40 and 80
-            // tiles at K >= 8192 the two were within 4 % either way and p8h kept them -- round 5: with gemm_i8_p8q2 the 128 x 128 tiles are ahead there too,
-            // 512 x 4096 x 11008 32.6 -> 30.6 us, 384 rows 27.3 -> 26.7 (profiles/r5_midsize_forced_kernels.txt), so the exception only remains for the
-            // one-barrier kernel (ASQ_P8Q2=0); OPT's K = 20480 stays with p8h's deeper split)
-            if (th >= 16 && th <= 128 && K < 16384 && !(!p8q2_enabled() && K >= 8192 && th >= 40 && th < 80)) return KERN_P8Q;
-            return KERN_P8H;
-        }
-        // 256 x 256 tiles: gemm_i8_p16, p8's schedule on v_mfma_i32_16x16x64_i8.  Under the socket power limit the GEMM's time is its energy, and the
-        // 16 x 16 x 64 instruction moves half the accumulator bytes per MAC: measured against p8 in one process (profiles/r3_p8_vs_p16_ab.txt, bit-identical
-        // outputs) 4096^3 56.8 -> 51.1 us, 8192 x 4096 x 4096 -8 %, 16384 x 12288 x 4096 -8 %, 4096 x 4096 x 8192 102.3 -> 92.0 (p4, the round-2 choice for
-        // K >= 8192 -- 128 x 128 per wave, a third fewer fragment bytes -- gained 1.7-3 % there).  launch_gemm sends what p16 does not carry (4-byte and
-        // int8 outputs, fp8 operands, K splits, grouped launches) to p8; p8 and p4 stay reachable through ASQ_GEMM_KERNEL.
-        return KERN_P16;
-    }
-    return KERN_GENERIC;
-}
-
-// shapes gemm_i8_p16 can run with offset operands (whether it SHOULD is offsets_profitable: the dispatcher's own choice of p16)
-static inline bool offsets_shape_ok(const void *x, const void *w, int64_t M, int64_t N, int64_t K)
-{
-    const bool aligned = ((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0;
-    return aligned && K % 128 == 0 && K >= 128 && K <= OFFSET_MAX_K && N % 4 == 0 && N >= 4 && M >= 1;
-}
-
-static inline int forced_ksplit()  // env ASQ_KSPLIT=n forces a split count (development / tuning aid)
-{
-    static int forced = -2;
-    if (forced == -2) {
-        const char *e = getenv("ASQ_KSPLIT");
-        forced = e ? atoi(e) : -1;
-    }
-    return forced;
-}
-
-// number of K splits for the tiled kernel: fill the 256 CUs when the M x N tile grid cannot
-static inline int pick_ksplit(int64_t tiles, int64_t K, int64_t M, int64_t N, size_t ws_bytes)
-{
-    if (N % 4 != 0) return 1;
-    const int64_t nt = K / 128;
-    {
-        const int forced = forced_ksplit();
-        if (forced > 0) {
-            int64_t f = forced > nt ? nt : forced;
-            while (f > 1 && (size_t)f * (size_t)M * (size_t)N * 4 > ws_bytes) --f;
-            return (int)f;
-        }
-    }
-    // measured on MI355X (ASQ_KSPLIT sweep, 128..2048 rows x LLaMA/OPT widths): the slab write +
-    // reduce pass costs ~2 x S x M x N x 4 B of traffic, so the optimum is ~130-200 blocks, not 256
-    if (tiles >= 118) return 1;
-    int64_t s = (176 + tiles / 2) / tiles;
-    if (s > nt / 4) s = nt / 4;              // >= 4 K-tiles (512 k) per split: keep the pipeline efficient
-    while (s > 1 && (size_t)s * (size_t)M * (size_t)N * 4 > ws_bytes) --s;
-    return s < 1 ? 1 : (int)s;
-}
-
-constexpr double P8Q_FIX_TAIL_US = 4.4, P8Q_FIX_PER_SPLIT_US = 1.1;   // in-launch tail of a tile split in two; per further split (fitted: profiles/r5_splitk_fix_sweep.txt)
-// K splits for the 128 x 128 kernel, from a small cost model fitted to measurements (us): a block costs 3 + (K-tiles) x (0.40 + 0.20 x the
-// fraction of the 256 CUs that hold a block -- the L2->LDS path is shared), a split launch adds the reduce pass, 5 + S x M x N x 4 B at
-// 3 TB/s.  512x4096x4096: S = 1 (18.0 us measured; S = 2: 21.3); 512x4096x11008: S = 2 (37.3; S = 1: 40.1); 128x4096x11008: S = 7 (21.9).
-// ASQ_SPLITK_FIX=0: K splits of the 128 x 128 kernel go back to slab launch + reduce launch (A/B switch).  Default 1: reduced inside the launch (asq_gemm_p8q2.h).
-static inline int splitk_fix_mode()
-{
-    static const int m = [] {
-        const char *e = getenv("ASQ_SPLITK_FIX");
-        return e ? atoi(e) : 1;
-    }();
-    return m;
-}
-// scratch bytes of the in-launch form: one 64 KiB register image per (tile, split)
-static inline size_t p8q_fix_bytes(int64_t tiles, int64_t s) { return (size_t)tiles * (size_t)s * 65536; }
-
-// `fix`: the caller can run the in-launch reduction (gemm_i8_p8q2<Epi, true>): a split then costs its tail (write-through image stores, one ticket, S - 1 image
-// reads by the last arriver) instead of a second launch and a round trip of the slabs.
-static inline int pick_ksplit_p8q(int64_t tiles, int64_t K, int64_t M, int64_t N, size_t ws_bytes, bool fix = false)
-{
-    if (N % 4 != 0) return 1;
-    const int64_t nt = K / 128;
-    const int forced = forced_ksplit();
-    int64_t s = 1;
-    if (forced > 0) {
-        s = forced > nt ? nt : forced;
-    } else {
-        double best = 1e30;
-        const int64_t smax = nt / 4 < 16 ? nt / 4 : 16;
-        for (int64_t c = 1; c <= (smax < 1 ? 1 : smax); ++c) {
-            const int64_t nblk = fix ? 8 * ((tiles + 7) / 8) * c : tiles * c;   // (the XCD-affine grid rounds every XCD's share up)
-            const double blocks = (double)nblk, waves = (double)((nblk + 255) / 256), fill = blocks < 256.0 ? blocks / 256.0 : 1.0;
-            double t = fix ? waves * (3.0 + (double)((nt + c - 1) / c) * (0.36 + 0.23 * (fill > 0.5 ? fill - 0.5 : 0.0)))   // (gemm_i8_p8q2's K-tile: flat up to half the chip)
-                           : waves * (3.0 + (double)((nt + c - 1) / c) * (0.40 + 0.20 * fill));
-            if (c > 1) t += fix ? P8Q_FIX_TAIL_US + P8Q_FIX_PER_SPLIT_US * (double)(c - 2) : 5.0 + (double)c * (double)M * (double)N * 4.0 / 3.0e6;
-            if (t < best) { best = t; s = c; }
-        }
-    }
-    if (fix) {
-        while (s > 1 && p8q_fix_bytes(tiles, s) > ws_bytes) --s;
-    } else {
-        while (s > 1 && (size_t)s * (size_t)M * (size_t)N * 4 > ws_bytes) --s;
-    }
-    return s < 1 ? 1 : (int)s;
-}
-
-// K splits for the 128-row kernel (tiles = its block count at one split), from the same kind of fitted cost model as pick_ksplit_p8q (us): a block
-// costs 3 + (K-tiles) x (0.45 + 0.33 x the fraction of the 256 CUs that hold a block), a split launch adds 5 + S x M x N x 4 B at 3 TB/s for the
-// reduce pass.  OPT-13B fc2 at 256 rows (40 tiles, 160 K-tiles): S = 6 (39.5 us warm / 46.0 cold; the former "fill ~192 CUs" rule gave S = 4:
-// 41.2 / 51.8); 384x4096x11008: S = 4 (31.4); 256x4096x11008: S = 6 (26.3); 2048x4096x4096 (128 tiles): S = 1.
-static inline int pick_ksplit_p8h(int64_t tiles, int64_t K, int64_t M, int64_t N, size_t ws_bytes)
-{
-    if (N % 4 != 0) return 1;
-    const int64_t nt = K / 128;
-    const int forced = forced_ksplit();
-    int64_t s = 1;
-    if (forced > 0) {
-        s = forced > nt ? nt : forced;
-    } else {
-        double best = 1e30;
-        const int64_t smax = nt / 4 < 16 ? nt / 4 : 16;
-        for (int64_t c = 1; c <= (smax < 1 ? 1 : smax); ++c) {
-            const double blocks = (double)tiles * (double)c, waves = (double)((tiles * c + 255) / 256), fill = blocks < 256.0 ? blocks / 256.0 : 1.0;
-            double t = waves * (3.0 + (double)((nt + c - 1) / c) * (0.45 + 0.33 * fill));
-            if (c > 1) t += 5.0 + (double)c * (double)M * (double)N * 4.0 / 3.0e6;
-            if (t < best) { best = t; s = c; }
-        }
-    }
-    while (s > 1 && (size_t)s * (size_t)M * (size_t)N * 4 > ws_bytes) --s;
-    return s < 1 ? 1 : (int)s;
-}
-// (K splits of this kernel reduced inside the launch were built on splitk_fix_reduce and measured: no gain at two splits, 3-7 us slower from three on -- 128 KiB images,
-// 40-80 tiles, 4-6 splits: profiles/r5_p8h_splitk_in_launch_dropped.txt)
+template <class Epi, class = void> struct IsGroupable : std::false_type {};
+template <class Epi> struct IsGroupable<Epi, std::enable_if_t<Epi::kGroupable>> : std::true_type {};
+template <class Epi, class = void> struct HasColView : std::false_type {};
+template <class Epi> struct HasColView<Epi, std::enable_if_t<Epi::kColView>> : std::true_type {};
+template <class Epi> constexpr EpiCaps epi_caps() { return EpiCaps{Epi::Mma::kIsInt, Epi::kOutBytes, Epi::kHasCol, Epi::kHasBias, HasColView<Epi>::value}; }
 
 template <class Epi, int MT, int NT> int launch_skinny_mt(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, int mblocks, const Epi &epi, hipStream_t s)
 {
@@ -1361,47 +1184,6 @@ template <class Epi, int MT, int NT> int launch_skinny_mt(const int8_t *x, const
     return ASQ_OK;
 }
 
-// ---- second-generation weight stream (asq_gemm_wstream.h): grid size and workspace
-struct WsPlan {
-    int G = 0, KU = 0, T = 0, maxseg = 0, mt = 0;
-    size_t bytes = 0;  // scratch behind the workspace header
-};
-static inline int ws_env(const char *name)  // development overrides, read once per process
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : -1;
-}
-static inline WsPlan plan_wstream(int64_t M, int64_t N, int64_t K)
-{
-    WsPlan p;
-    if (M < 1 || M > 128 || K % 128 != 0 || K < 128) return p;
-    // Used where its in-launch reduction (~4 us) costs less than gemm_i8_skinny's LDS starvation: long-K weights at >= 16 rows.  Measured, cold
-    // weights, us (tools/ubench/wstream_probe, profiles/r3_skinny_experiments.md): 5120x20480 (OPT-13B fc2) 16 rows 26.5 -> 24.0, 32 rows 31.3 -> 25.9;
-    // 4096x14336 (Mixtral w2) 64 rows 22.5 -> 20.0; everything else +3 ... +90 % (4096x4096 at 32 rows: 6.5 -> 12.0): the region is narrow on purpose.
-    static const int impl = ws_env("ASQ_SK_IMPL");  // development A/B: 0 = never, 1 = wherever it can run
-    const bool region = (K >= 4 * N && M >= 16 && N * K >= (64ll << 20)) || (K >= 3 * N && M > 32 && N * K >= (48ll << 20));
-    if (impl == 0 || !(region || impl == 1)) return p;
-    const int64_t NG = (N + WS_CB - 1) / WS_CB, KU = K / 128, T = NG * KU;
-    if (NG > WS_MAX_GROUPS || T >= (1ll << 22)) return p;  // (T * G < 2^31 with G <= 512)
-    static const int forced_g = ws_env("ASQ_WS_GRID");
-    int64_t G = forced_g > 0 ? forced_g : 256;
-    if (G > 512) G = 512;
-    if (forced_g <= 0) {
-        // at least 4 units (64 KB of W) per block, and at most ~16 contributors per group for the last arriver to sum
-        if (G > T / 4) G = T / 4 < 1 ? 1 : T / 4;
-        if (G > 15 * NG) G = 15 * NG;
-    }
-    if (G > T) G = T;
-    p.G = (int)G;
-    p.KU = (int)KU;
-    p.T = (int)T;
-    const int64_t nun_max = (T + G - 1) / G;
-    p.maxseg = (int)((nun_max + KU - 1) / KU + 1);
-    p.mt = M <= 16 ? 1 : M <= 32 ? 2 : M <= 64 ? 4 : 8;
-    p.bytes = (size_t)G * (size_t)p.maxseg * (size_t)(p.mt * 8192);
-    return p;
-}
-
 template <class Epi, int MT, bool WNT>
 int launch_wstream_mt(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const WsPlan &p, char *ws, const Epi &epi, hipStream_t s)
 {
@@ -1415,37 +1197,21 @@ int launch_wstream_mt(const int8_t *x, const int8_t *w, int64_t M, int64_t N, in
     return ASQ_OK;
 }
 
-// ws_hdr = the caller's workspace (header first), usable scratch behind it = ws_bytes - WS_HEADER_BYTES
-template <class Epi> int launch_skinny(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const Epi &epi, hipStream_t s, void *ws_hdr = nullptr, size_t ws_bytes = 0)
+// the weight stream as planned: the stream-K kernel over the caller's workspace (p.ws.G > 0; ws_hdr = the workspace, header first) or the first-generation kernel
+template <class Epi> int launch_skinny(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const Epi &epi, hipStream_t s, void *ws_hdr)
 {
-    const int mblocks = (int)((M + 63) / 64);                       // m-blocks of <= 64 rows, balanced
-    const int mt = (int)(((M + mblocks - 1) / mblocks + 15) / 16);  // 16-row tiles per m-block
-    static int nt_forced = -1;
-    if (nt_forced < 0) { const char *e = getenv("ASQ_SK_NT"); nt_forced = e ? atoi(e) : 0; }
-    const int64_t items2 = ((N + 31) / 32) * mblocks;
-    const bool wide = nt_forced ? nt_forced == 2 : (items2 >= 448 || (K >= 16384 && items2 >= 128));
-    if constexpr (Epi::Mma::kIsInt) if (ws_hdr != nullptr && ws_bytes > (size_t)WS_HEADER_BYTES && M * K < (1ll << 32)) {
-        const WsPlan p = plan_wstream(M, N, K);  // the stream-K kernel inside its measured region (plan_wstream)
-        if (p.G > 0 && p.bytes <= ws_bytes - WS_HEADER_BYTES) {
-            // streaming (nt) cache policy for the weight lines of the big streams: 5120x20480 (105 MB) 27.2 -> 25.9 us at 32 rows, 25.8 -> 24.0 at 16;
-            // 4096x14336 (59 MB) 20.0 -> 21.9 at 64 rows, so only above 80 MB
-            static const int nt_env = ws_env("ASQ_WS_NT");
-            const int nt = nt_env >= 0 ? nt_env : (N * K >= (80ll << 20) ? 1 : 0);
-#define ASQ_WS(MT_) (nt == 1 ? launch_wstream_mt<Epi, MT_, true>(x, w, M, N, K, p, (char *)ws_hdr, epi, s) : launch_wstream_mt<Epi, MT_, false>(x, w, M, N, K, p, (char *)ws_hdr, epi, s))
-            switch (p.mt) {
-            case 1: return ASQ_WS(1);
-            case 2: return ASQ_WS(2);
-            case 4: return ASQ_WS(4);
-            default: return ASQ_WS(8);
-            }
-#undef ASQ_WS
+    if constexpr (Epi::Mma::kIsInt) if (p.ws.G > 0) {
+#define ASQ_WS(MT_) (p.wide ? launch_wstream_mt<Epi, MT_, true>(x, w, M, N, K, p.ws, (char *)ws_hdr, epi, s) : launch_wstream_mt<Epi, MT_, false>(x, w, M, N, K, p.ws, (char *)ws_hdr, epi, s))
+        switch (p.ws.mt) {
+        case 1: return ASQ_WS(1);
+        case 2: return ASQ_WS(2);
+        case 4: return ASQ_WS(4);
+        default: return ASQ_WS(8);
         }
+#undef ASQ_WS
     }
-    // 32 channels per item halve the X re-reads from L2.  Measured (tools/ubench/skinny_probe, ASQ_SK_NT=1|2, M = 32):
-    // 14336x4096 16.8 -> 15.5 us, 20480x5120 29.5 -> 26.3, 5120x20480 40.9 -> 31.7; but 8192x8192 18.0 -> 20.6 and
-    // 4096x11008 13.1 -> 15.5 (too few items), 11008x4096 unchanged: only with plenty of items, or a long K
-#define ASQ_SK(MT_) (wide ? launch_skinny_mt<Epi, MT_, 2>(x, w, M, N, K, mblocks, epi, s) : launch_skinny_mt<Epi, MT_, 1>(x, w, M, N, K, mblocks, epi, s))
-    switch (mt) {
+#define ASQ_SK(MT_) (p.wide ? launch_skinny_mt<Epi, MT_, 2>(x, w, M, N, K, p.mblocks, epi, s) : launch_skinny_mt<Epi, MT_, 1>(x, w, M, N, K, p.mblocks, epi, s))
+    switch (p.mt) {
     case 1: return ASQ_SK(1);
     case 2: return ASQ_SK(2);
     case 3: return ASQ_SK(3);
@@ -1454,133 +1220,29 @@ template <class Epi> int launch_skinny(const int8_t *x, const int8_t *w, int64_t
 #undef ASQ_SK
 }
 
-// Tail peel (hybrid of data-parallel tiles and a finer-grained remainder).  A tile grid that is a few tiles over a multiple of 256 pays a whole
-// extra wave for them (1536 x 11008: 258 tiles -> 90 us against 51 us for the 172 tiles of 1024 rows).  When the last wave would be < 3/8 full
-// and <= 48 tiles cover it, the last `c` tile columns (all of the remainder and a little more) become their own launch of 128 x 128 tiles (p8q:
-// four times as many blocks, with its usual K split when the caller's workspace allows one) and the main launch is left with <= 256 * waves tiles.
-struct TailPeel {
-    int64_t n_main = 0;  // columns [0, n_main) stay with the main launch; 0 = no peel
-    size_t ws_bytes = 0; // workspace that lets the remainder split K (optional)
-    bool rem_p8h = false; // the remainder runs on 128 x 256 tiles (gemm_i8_p8h) instead of 128 x 128 (gemm_i8_p8q)
+// Grouped launches of gemm_i8_p8: the grid, a host-side upper bound on the number of tiles, and whether the tail tiles may split K through the caller's workspace.
+struct GroupedGrid {
+    int64_t tiles;
+    bool tail_split;
 };
-static inline TailPeel plan_tail_peel(GemmKernel kern, int64_t M, int64_t N, int64_t K)
+static inline GroupedGrid grouped_grid(int64_t M, int64_t N, int ngroups, bool is_int, bool has_header, size_t scratch_bytes)
 {
-    TailPeel p;
-    // (the remainder launch costs ~13 us at K = 4096; the extra wave it replaces ~20 us for the 128-row kernel, 35-45 us for the 256-row ones)
-    if (kern != KERN_P8 && kern != KERN_P4 && kern != KERN_P8H && kern != KERN_P16 && kern != KERN_P4X16) return p;
-    static const bool disabled = getenv("ASQ_NO_TAIL") != nullptr;  // development / A-B aid
-    if (disabled || forced_kernel() >= 0 || forced_ksplit() > 0 || N % 4 != 0 || K < 4096) return p;  // (a short K loop makes the extra wave cheap)
-    const int64_t rows = kern == KERN_P8H ? 128 : 256;
-    const int64_t tm = (M + rows - 1) / rows, tn = (N + 255) / 256, tiles = tm * tn;
-    const int64_t full = tiles / 256, r = tiles % 256;
-    // Round 4 (profiles/r4_tail_sweep.txt, 2048 rows x (32 + c) tile columns, K = 4096, remainder = 8 c tiles of 256 x 256): as 128 x 128 tiles (p8q, four times
-    // the blocks) the remainder gains 21 ... 14 % up to 64 tiles and nothing beyond; as 128 x 256 tiles (p8h, ONE round of twice the blocks) 11 ... 7 % from 88 to
-    // 128 tiles; from 160 tiles on both lose to the plain second round.
-    const int64_t r_max = rows == 256 ? 128 : 96;
-    if (full < 1 || r == 0 || r > r_max) return p;
-    const int64_t c = (r + tm - 1) / tm;
-    const int64_t rem256 = ((M + 255) / 256) * c;   // the remainder in 256 x 256 tiles' worth
-    if (c >= tn || rem256 > (rows == 256 ? 128 : 48)) return p;
-    p.rem_p8h = rem256 > 64;
-    p.n_main = (tn - c) * 256;
-    const int64_t n_rem = N - p.n_main;
-    const int ks = p.rem_p8h ? pick_ksplit_p8h(((M + 127) / 128) * ((n_rem + 255) / 256), K, M, n_rem, (size_t)-1)
-                             : pick_ksplit_p8q(((M + 127) / 128) * ((n_rem + 127) / 128), K, M, n_rem, (size_t)-1);
-    p.ws_bytes = ks > 1 ? (size_t)ks * (size_t)M * (size_t)n_rem * 4 : 0;
-    if (!p.rem_p8h) {   // a 128 x 128 remainder reduces its K splits inside its launch when the caller's workspace has a header (register images of whole tiles, their own split count)
-        const int64_t tiles = ((M + 127) / 128) * ((n_rem + 127) / 128);
-        const int kf = tiles > WS_MAX_GROUPS ? 1 : pick_ksplit_p8q(tiles, K, M, n_rem, (size_t)-1, true);
-        const size_t fb = kf > 1 ? p8q_fix_bytes(tiles, kf) : 0;
-        p.ws_bytes = fb > p.ws_bytes ? fb : p.ws_bytes;
+    GroupedGrid g{(M / 256 + ngroups) * ((N + 255) / 256), false};   // upper bound on sum ceil(m_g / 256) * tn
+    if (ngroups <= P8_GROUPED_SCAN_MAX) {       // balanced scheduler: blocks b = 8 * slot + xcd, up to one extra round of K pieces per XCD
+        g.tiles = 8 * ((g.tiles + 7) / 8 + 2 + P8_CUS_PER_XCD);   // (+2: full and half tiles are dealt to the XCDs separately)
+        g.tail_split = is_int && has_header && scratch_bytes >= P8_GROUPED_WS_BYTES && grouped_tail_split_enabled();
     }
-    return p;
+    return g;
 }
 
-// ASQ_MMA=32: the tiled int8 kernels other than p16 / p8 / p4 themselves (grouped launches, p8h, p8q) keep v_mfma_i32_32x32x32_i8 instead of the 16 x 16 x 64 form
-// (development / A-B aid; read once)
-static inline bool mma32_forced()
-{
-    static const bool v = [] { const char *e = getenv("ASQ_MMA"); return e && atoi(e) == 32; }();
-    return v;
-}
-
-// ASQ_GROUPED_SPLIT=0: grouped launches never split the K loop of their tail tiles (A/B switch; the default is on when a workspace is passed)
-static inline bool grouped_tail_split_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("ASQ_GROUPED_SPLIT");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-template <class Epi, class = void> struct IsGroupable : std::false_type {};
-template <class Epi> struct IsGroupable<Epi, std::enable_if_t<Epi::kGroupable>> : std::true_type {};
-template <class Epi, class = void> struct HasColView : std::false_type {};
-template <class Epi> struct HasColView<Epi, std::enable_if_t<Epi::kColView>> : std::true_type {};
-
-// A caller's workspace is [ header WS_HEADER_BYTES (asq_workspace_init: magic + tickets of the weight-streaming kernel) | scratch ];
-// `ws` below is the scratch part (split-K slabs), `ws_hdr` the whole thing (null when the caller's buffer is too small to hold a header).
+// One planned launch over the output columns the caller has re-based x / w / epi / N to.  `ws_hdr`: the caller's workspace (header first), `ws`: the scratch behind the header.
 template <class Epi>
-int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, Epi epi, hipStream_t s, const char *what, void *ws_hdr, void *ws,
-                     size_t ws_bytes, const int *goffs = nullptr, int ngroups = 0, int peel_role = 0 /* 0 top level, 1 main part, 2 / 3 remainder (128 x 128 / 128 x 256 tiles) */,
-                     OffsetArgs off = OffsetArgs{})
+int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const Epi &epi, hipStream_t s, const char *what, void *ws_hdr, void *ws,
+                const OffsetArgs &off)
 {
-    if (M == 0 || N == 0) return ASQ_OK;
-    if constexpr (!IsGroupable<Epi>::value) {
-        ASQ_REQUIRE(goffs == nullptr, ASQ_ERR_DIM, "%s: this epilogue has no grouped form", what);
-    } else if (goffs != nullptr) {  // grouped: tiled kernel only; grid = host-side upper bound on the number of tiles
-        const bool ok = (((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0) && K % 128 == 0 && K >= 128 && K <= (1 << 24);
-        ASQ_REQUIRE(ok, ASQ_ERR_DIM, "%s: grouped launch needs K %% 128 == 0 and 16-B aligned operands", what);
-        const int64_t tn = (N + 255) / 256;
-        int64_t tiles = (M / 256 + ngroups) * tn;   // upper bound on sum ceil(m_g / 256) * tn
-        char *gws = nullptr;
-        if (ngroups <= P8_GROUPED_SCAN_MAX) {       // balanced scheduler: blocks b = 8 * slot + xcd, up to one extra round of K pieces per XCD
-            tiles = 8 * ((tiles + 7) / 8 + 2 + P8_CUS_PER_XCD);   // (+2: full and half tiles are dealt to the XCDs separately)
-            if constexpr (Epi::Mma::kIsInt)
-                if (ws_hdr != nullptr && ws_bytes >= P8_GROUPED_WS_BYTES && grouped_tail_split_enabled()) gws = (char *)ws_hdr;
-        }
-        ASQ_REQUIRE(tiles < (1ll << 24), ASQ_ERR_DIM, "%s: too many tiles", what);
-        // int8 groups run on v_mfma_i32_16x16x64_i8 (the L16 form of the kernel: asq_gemm_p16.h for why); ASQ_MMA=32 keeps the 32 x 32 x 32 form (A/B)
-        auto kfn = gemm_i8_p8<Epi, 0, true>;
-        if constexpr (Epi::Mma::kIsInt) {
-            if (!mma32_forced()) kfn = gemm_i8_p8<Epi, 0, true, true>;
-        }
-        hipError_t e = ensure_dynamic_lds((const void *)kfn, P8_LDS_BYTES);
-        if (e != hipSuccess) {
-            asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-            return (int)e;
-        }
-        bool g_offs = false;
-        if constexpr (Epi::Mma::kIsInt && Epi::kOutBytes == 2) g_offs = off.row != nullptr && !mma32_forced();
-        ASQ_REQUIRE(off.row == nullptr || (g_offs && K <= OFFSET_MAX_K && N % 4 == 0), ASQ_ERR_DIM, "%s: offset operands need int8 groups, 2-byte outputs, K <= 65536, N %% 4 == 0", what);
-        if (g_offs) {
-            e = ensure_dynamic_lds((const void *)kfn, P16_LDS_BYTES);
-            if (e != hipSuccess) {
-                asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-                return (int)e;
-            }
-        }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)tiles), dim3(512), g_offs ? P16_LDS_BYTES : P8_LDS_BYTES, s, x, w, M, N, K, 0, (int)tn, 1, goffs, ngroups, gws, epi, g_offs ? off : OffsetArgs{});
-        return asq_after_launch(s, what);
-    }
     constexpr bool kInt = Epi::Mma::kIsInt;
-    GemmKernel kern = peel_role == 2 ? KERN_P8Q : peel_role == 3 ? KERN_P8H : pick_kernel(x, w, M, N, K);   // (2 / 3: the column remainder of a tail peel)
-    if (off.row != nullptr) {   // offset operands: gemm_i8_p16 only (the entry point has checked the shape: offsets_supported)
-        ASQ_REQUIRE(kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4) && offsets_shape_ok(x, w, M, N, K), ASQ_ERR_DIM, "%s: offset operands need the 256 x 256 kernel (2- or 4-byte output, K %% 128 == 0, K <= 65536, N %% 4 == 0, aligned operands)", what);
-        kern = KERN_P16;
-    }
-    if constexpr (kInt && HasColView<Epi>::value) {
-        if (off.row == nullptr && peel_role == 0 && (N * Epi::kOutBytes) % 16 == 0) {
-            const TailPeel tp = plan_tail_peel(kern, M, N, K);
-            if (tp.n_main > 0) {
-                const int rc = launch_gemm_impl(x, w, M, tp.n_main, K, epi, s, what, nullptr, nullptr, 0, nullptr, 0, 1);
-                if (rc) return rc;
-                return launch_gemm_impl(x, w + tp.n_main * K, M, N - tp.n_main, K, epi.col_view(tp.n_main), s, what, ws_hdr, ws, ws_bytes, nullptr, 0, tp.rem_p8h ? 3 : 2);
-            }
-        }
-    }
-    // ---- the tiled kernels: one launcher (dynamic-LDS attribute once per kernel, launch) and one split-K tail (exact int32 slabs, then reduce + the caller's epilogue)
+    constexpr bool kP4 = kInt && Epi::kOutBytes == 2, kP4X = kP4 && !Epi::kHasCol && !Epi::kHasBias, kP16 = kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4);   // (plan_gemm's fallbacks)
+    // the tiled kernels: one launcher (dynamic-LDS attribute once per kernel, launch) and one split-K tail (exact int32 slabs, then reduce + the caller's epilogue)
     auto launch_tiled = [&](auto kfn, int lds_attr, int lds, int64_t grid, int block, auto... args) -> int {
         ASQ_REQUIRE(grid < (1ll << 24), ASQ_ERR_DIM, "%s: too many tiles", what);
         const hipError_t e = ensure_dynamic_lds((const void *)kfn, lds_attr);
@@ -1591,141 +1253,145 @@ int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int
         hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)block), lds, s, x, w, M, N, K, args...);
         return ASQ_OK;
     };
-    auto reduce_slabs = [&](int ksplit) {
-        if constexpr (kInt) {
-            int64_t blocks = (M * (N / 4) + 255) / 256;
-            if (blocks > 8192) blocks = 8192;
-            hipLaunchKernelGGL((splitk_reduce<Epi>), dim3((unsigned)blocks), dim3(256), 0, s, (const int32_t *)ws, ksplit, M, N, epi);
-        }
-    };
-    const bool ws_ok = kInt && ws != nullptr && (((uintptr_t)ws) & 15) == 0;
     const int64_t tm256 = (M + 255) / 256, tm128 = (M + 127) / 128, tn256 = (N + 255) / 256, tn128 = (N + 127) / 128;
+    const bool slabs = p.split == SPLIT_SLABS;
     [[maybe_unused]] const EpiI32 slab{(int32_t *)ws, N, true};
     const int *const no_groups = nullptr;
     char *const no_gws = nullptr;
     const uint8_t *const no_mx = nullptr;
+    // each tiled kernel's launch, over the kernel form (the plan's MFMA form and split form select it) and the epilogue it runs: the caller's, or the slab writer
+    [[maybe_unused]] auto p8 = [&](auto kfn, const auto &e) {
+        return launch_tiled(kfn, P8_LDS_BYTES, P8_LDS_BYTES, tm256 * tn256 * p.ksplit, 512, (int)tm256, (int)tn256, p.ksplit, no_groups, 0, no_gws, e, OffsetArgs{});
+    };
+    [[maybe_unused]] auto p8h = [&](auto kfn, const auto &e) { return launch_tiled(kfn, P8H_LDS_BYTES, P8H_LDS_BYTES, tm128 * tn256 * p.ksplit, 512, (int)tm128, (int)tn256, p.ksplit, e); };
+    [[maybe_unused]] auto p8q = [&](auto kfn, const auto &e) { return launch_tiled(kfn, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128 * p.ksplit, 512, (int)tm128, (int)tn128, p.ksplit, e, no_mx, no_mx); };
+    [[maybe_unused]] auto p8q2 = [&](auto kfn, const auto &e, char *hdr) {   // (in-launch reduction: the XCD-affine grid rounds every XCD's share of the tiles up)
+        return launch_tiled(kfn, P8Q_LDS_BYTES, P8Q_LDS_BYTES, (hdr ? 8 * ((tm128 * tn128 + 7) / 8) : tm128 * tn128) * p.ksplit, 512, (int)tm128, (int)tn128, p.ksplit, e, hdr);
+    };
     int rc = ASQ_OK;
-
-    constexpr bool kP4 = kInt && Epi::kOutBytes == 2;  // the 4-wave kernels: int8 operands, 2-byte outputs (their row epilogue; the int32 / int8-out
-                                                       // epilogues next to 256 accumulator registers would spill)
-    if (kern == KERN_P4 && !kP4) kern = KERN_P8;
-    // four waves x 128 x 128 on the 16 x 16 x 64 instruction (asq_gemm_p4x16.h): scalar / per-token scale epilogues with 2-byte outputs; otherwise p16
-    constexpr bool kP4X = kP4 && !Epi::kHasCol && !Epi::kHasBias;
-    if (kern == KERN_P4X16 && !kP4X) kern = KERN_P16;
-    // the 256 x 256 kernel on v_mfma_i32_16x16x64_i8 (asq_gemm_p16.h): plain launches with 2- and (round 4, epilogue_wave_rows4) 4-byte outputs; what it does not
-    // carry -- int8 outputs, K splits -- runs on p8, in its L16 mode (the same instruction) unless the 32 x 32 x 32 form was asked for
-    constexpr bool kP16 = kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4);
-    bool p8_l16 = false;
-    if (kern == KERN_P16 && !kP16) {
-        kern = KERN_P8;
-        p8_l16 = kInt && !mma32_forced();
-    }
-    ASQ_REQUIRE(off.row == nullptr || kern == KERN_P16, ASQ_ERR_DIM, "%s: offset operands: no kernel", what);
-
-    if (kern == KERN_P4) {
+    switch (p.kern) {
+    case KERN_P4:
         if constexpr (kP4) rc = launch_tiled(gemm_i8_p4<Epi>, P4_LDS_BYTES, P4_LDS_BYTES, tm256 * tn256, 256, (int)tm256, (int)tn256, epi);
-    } else if (kern == KERN_P4X16) {
+        break;
+    case KERN_P4X16:
         if constexpr (kP4X) rc = launch_tiled(gemm_i8_p4x16<Epi>, P4_LDS_BYTES, P4_LDS_BYTES, tm256 * tn256, 256, (int)tm256, (int)tn256, epi);
-    } else if (kern == KERN_P16) {
-        bool done = false;
+        break;
+    case KERN_P16:
         if constexpr (kP16 && Epi::kOutBytes == 2) {
-            // multi-round launches without edge tiles: the persistent form (asq_gemm_p16p.h) -- the next tile's first K-tile and epilogue operands arrive under
-            // this tile's last K-tile and epilogue.  ASQ_P16_PERSIST=0 keeps gemm_i8_p16 (A/B); =2 also takes single-round launches (development).
-            static const int persist = [] { const char *e = getenv("ASQ_P16_PERSIST"); return e ? atoi(e) : 1; }();
-            const int64_t T = tm256 * tn256;
-            if (persist && M % 256 == 0 && N % 256 == 0 && K % 256 == 0 && (T > 8 * P8_CUS_PER_XCD || persist == 2) && ((((uintptr_t)epi.out) & 15) == 0) && (epi.N * 2) % 16 == 0 &&
-                epi.N * 2 < (int64_t(1) << 24)) {
-                const int64_t grid = T < 8 * P8_CUS_PER_XCD ? T : 8 * P8_CUS_PER_XCD;
-                rc = launch_tiled(gemm_i8_p16p<Epi>, P16P_LDS_BYTES, P16P_LDS_BYTES, grid, 512, (int)tm256, (int)tn256, epi, off);
-                done = true;
+            if (p.persistent) {
+                rc = launch_tiled(gemm_i8_p16p<Epi>, P16P_LDS_BYTES, P16P_LDS_BYTES, persistent_grid(tm256 * tn256), 512, (int)tm256, (int)tn256, epi, off);
+                break;
             }
         }
-#if ASQ_P16_TAIL
-        if constexpr (kP16 && Epi::kOutBytes == 2) {   // (builds with -DASQ_P16_TAIL=1 only: asq_gemm_p16t.h, measured and NOT shipped, profiles/r6_tail_overlap_ab.txt)
-            static const int tail = [] { const char *e = getenv("ASQ_P16_TAIL"); return e ? atoi(e) : 1; }();
-            if (!done && tail && M % 256 == 0 && N % 256 == 0 && K % 256 == 0 && K >= 512 && ((((uintptr_t)epi.out) & 15) == 0) && (epi.N * 2) % 16 == 0 && epi.N * 2 < (int64_t(1) << 24)) {
-                rc = launch_tiled(gemm_i8_p16t<Epi>, P16_LDS_BYTES, off.row ? P16_LDS_BYTES : P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, epi, off);
-                done = true;
-            }
-        }
-#endif
-        if constexpr (kP16) if (!done) rc = launch_tiled(gemm_i8_p16<Epi>, P16_LDS_BYTES, off.row ? P16_LDS_BYTES : P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, epi, off);
-    } else if (kern == KERN_P8) {
-        const int ksplit = ws_ok ? pick_ksplit(tm256 * tn256, K, M, N, ws_bytes) : 1;
-        if (ksplit > 1) {
-            if constexpr (kInt) {
-                rc = p8_l16 ? launch_tiled(gemm_i8_p8<EpiI32, 0, false, true>, P8_LDS_BYTES, P8_LDS_BYTES, tm256 * tn256 * ksplit, 512, (int)tm256, (int)tn256, ksplit, no_groups, 0, no_gws, slab, OffsetArgs{})
-                            : launch_tiled(gemm_i8_p8<EpiI32>, P8_LDS_BYTES, P8_LDS_BYTES, tm256 * tn256 * ksplit, 512, (int)tm256, (int)tn256, ksplit, no_groups, 0, no_gws, slab, OffsetArgs{});
-                if (rc == ASQ_OK) reduce_slabs(ksplit);
-            }
+        if constexpr (kP16) rc = launch_tiled(gemm_i8_p16<Epi>, P16_LDS_BYTES, off.row ? P16_LDS_BYTES : P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, epi, off);
+        break;
+    case KERN_P8:
+        if (slabs) {
+            if constexpr (kInt) rc = p.l16 ? p8(gemm_i8_p8<EpiI32, 0, false, true>, slab) : p8(gemm_i8_p8<EpiI32>, slab);
         } else {
-            bool done = false;
             if constexpr (kInt && !kP16) {   // (int8 outputs at p16's sizes)
-                if (p8_l16) {
-                    rc = launch_tiled(gemm_i8_p8<Epi, 0, false, true>, P8_LDS_BYTES, P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, 1, no_groups, 0, no_gws, epi, OffsetArgs{});
-                    done = true;
+                if (p.l16) {
+                    rc = p8(gemm_i8_p8<Epi, 0, false, true>, epi);
+                    break;
                 }
             }
-            if (!done) rc = launch_tiled(gemm_i8_p8<Epi>, P8_LDS_BYTES, P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, 1, no_groups, 0, no_gws, epi, OffsetArgs{});
+            rc = p8(gemm_i8_p8<Epi>, epi);
         }
-    } else if (kern == KERN_P8H) {
-        const int ksplit = ws_ok ? pick_ksplit_p8h(tm128 * tn256, K, M, N, ws_bytes) : 1;
-        if (ksplit > 1) {
-            if constexpr (kInt) {
-                rc = mma32_forced() ? launch_tiled(gemm_i8_p8h<EpiI32>, P8H_LDS_BYTES, P8H_LDS_BYTES, tm128 * tn256 * ksplit, 512, (int)tm128, (int)tn256, ksplit, slab)
-                                    : launch_tiled(gemm_i8_p8h<EpiI32, false, true>, P8H_LDS_BYTES, P8H_LDS_BYTES, tm128 * tn256 * ksplit, 512, (int)tm128, (int)tn256, ksplit, slab);
-                if (rc == ASQ_OK) reduce_slabs(ksplit);
-            }
+        break;
+    case KERN_P8H:
+        if (slabs) {
+            if constexpr (kInt) rc = p.l16 ? p8h(gemm_i8_p8h<EpiI32, false, true>, slab) : p8h(gemm_i8_p8h<EpiI32>, slab);
         } else {
-            bool done = false;
             if constexpr (kInt) {
-                if (!mma32_forced()) {
-                    rc = launch_tiled(gemm_i8_p8h<Epi, false, true>, P8H_LDS_BYTES, P8H_LDS_BYTES, tm128 * tn256, 512, (int)tm128, (int)tn256, 1, epi);
-                    done = true;
+                if (p.l16) {
+                    rc = p8h(gemm_i8_p8h<Epi, false, true>, epi);
+                    break;
                 }
             }
-            if (!done) rc = launch_tiled(gemm_i8_p8h<Epi>, P8H_LDS_BYTES, P8H_LDS_BYTES, tm128 * tn256, 512, (int)tm128, (int)tn256, 1, epi);
+            rc = p8h(gemm_i8_p8h<Epi>, epi);
         }
-    } else if (kern == KERN_P8Q) {
-        bool fix = false;
-        if constexpr (kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4)) fix = ws_ok && ws_hdr != nullptr && splitk_fix_mode() != 0 && p8q2_enabled() && !mma32_forced() && tm128 * tn128 <= WS_MAX_GROUPS;
-        int ksplit = ws_ok ? pick_ksplit_p8q(tm128 * tn128, K, M, N, ws_bytes, fix) : 1;
-        if (fix && (ksplit > 16 || p8q_fix_bytes(tm128 * tn128, ksplit) >= ((size_t)1 << 31))) {   // (32-bit image offsets; only a forced ASQ_KSPLIT gets here)
-            fix = false;
-            ksplit = pick_ksplit_p8q(tm128 * tn128, K, M, N, ws_bytes, false);   // (the slab form sizes its scratch differently)
-        }
-        if (ksplit > 1 && fix) {
-            if constexpr (kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4))
-                rc = launch_tiled(gemm_i8_p8q2<Epi, true>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, 8 * ((tm128 * tn128 + 7) / 8) * ksplit, 512, (int)tm128, (int)tn128, ksplit, epi, (char *)ws_hdr);
-        } else if (ksplit > 1) {
-            if constexpr (kInt) {
-                rc = mma32_forced() ? launch_tiled(gemm_i8_p8q<EpiI32>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128 * ksplit, 512, (int)tm128, (int)tn128, ksplit, slab, no_mx, no_mx)
-                     : p8q2_enabled() ? launch_tiled(gemm_i8_p8q2<EpiI32>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128 * ksplit, 512, (int)tm128, (int)tn128, ksplit, slab, (char *)nullptr)
-                                      : launch_tiled(gemm_i8_p8q<EpiI32, false, true>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128 * ksplit, 512, (int)tm128, (int)tn128, ksplit, slab, no_mx, no_mx);
-                if (rc == ASQ_OK) reduce_slabs(ksplit);
-            }
+        break;
+    case KERN_P8Q:
+        if (p.split == SPLIT_IN_LAUNCH) {
+            if constexpr (kP16) rc = p8q2(gemm_i8_p8q2<Epi, true>, epi, (char *)ws_hdr);
+        } else if (slabs) {
+            if constexpr (kInt) rc = p.l16 ? p8q2(gemm_i8_p8q2<EpiI32>, slab, nullptr) : p8q(gemm_i8_p8q<EpiI32>, slab);
         } else {
-            bool done = false;
             if constexpr (kInt) {
-                if (!mma32_forced()) {
-                    rc = p8q2_enabled() ? launch_tiled(gemm_i8_p8q2<Epi>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128, 512, (int)tm128, (int)tn128, 1, epi, (char *)nullptr)
-                                        : launch_tiled(gemm_i8_p8q<Epi, false, true>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128, 512, (int)tm128, (int)tn128, 1, epi, no_mx, no_mx);
-                    done = true;
+                if (p.l16) {
+                    rc = p8q2(gemm_i8_p8q2<Epi>, epi, nullptr);
+                    break;
                 }
             }
-            if (!done) rc = launch_tiled(gemm_i8_p8q<Epi>, P8Q_LDS_BYTES, P8Q_LDS_BYTES, tm128 * tn128, 512, (int)tm128, (int)tn128, 1, epi, no_mx, no_mx);
+            rc = p8q(gemm_i8_p8q<Epi>, epi);
         }
-    } else if (kern == KERN_SKINNY) {
-        const int rc = launch_skinny(x, w, M, N, K, epi, s, ws_hdr, ws_hdr ? ws_bytes + WS_HEADER_BYTES : 0);
-        if (rc) return rc;
-    } else {
+        break;
+    case KERN_SKINNY:
+        rc = launch_skinny(p, x, w, M, N, K, epi, s, ws_hdr);
+        break;
+    default: {
         const bool fast = (K % 16 == 0) && (((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0);
         dim3 grid((unsigned)((N + GEN_T - 1) / GEN_T), (unsigned)((M + GEN_T - 1) / GEN_T));
         ASQ_REQUIRE(grid.y < 65536, ASQ_ERR_DIM, "%s: M too large for the generic kernel (K %% 128 != 0 or unaligned operands)", what);
         hipLaunchKernelGGL((gemm_i8_generic<Epi>), grid, dim3(256), 0, s, x, w, M, N, K, fast, epi);
     }
+    }
+    if constexpr (kInt) {
+        if (rc == ASQ_OK && slabs) {   // sum the slabs, run the caller's epilogue
+            int64_t blocks = (M * (N / 4) + 255) / 256;
+            if (blocks > 8192) blocks = 8192;
+            hipLaunchKernelGGL((splitk_reduce<Epi>), dim3((unsigned)blocks), dim3(256), 0, s, (const int32_t *)ws, p.ksplit, M, N, epi);
+        }
+    }
     if (rc != ASQ_OK) return rc;
     return asq_after_launch(s, what);
+}
+
+// A caller's workspace is [ header WS_HEADER_BYTES (asq_workspace_init: magic + tickets of the in-launch reductions) | scratch ];
+// `ws` below is the scratch part, `ws_hdr` the whole thing (null when the caller's buffer is too small to hold a header).
+template <class Epi>
+int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, Epi epi, hipStream_t s, const char *what, void *ws_hdr, void *ws,
+                     size_t ws_bytes, const int *goffs = nullptr, int ngroups = 0, OffsetArgs off = OffsetArgs{})
+{
+    if (M == 0 || N == 0) return ASQ_OK;
+    constexpr bool kInt = Epi::Mma::kIsInt;
+    const bool aligned16 = ((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0;
+    if constexpr (!IsGroupable<Epi>::value) {
+        ASQ_REQUIRE(goffs == nullptr, ASQ_ERR_DIM, "%s: this epilogue has no grouped form", what);
+    } else if (goffs != nullptr) {  // grouped: tiled kernel only
+        ASQ_REQUIRE(aligned16 && K % 128 == 0 && K >= 128 && K <= (1 << 24), ASQ_ERR_DIM, "%s: grouped launch needs K %% 128 == 0 and 16-B aligned operands", what);
+        const GroupedGrid gg = grouped_grid(M, N, ngroups, kInt, ws_hdr != nullptr, ws_bytes);
+        ASQ_REQUIRE(gg.tiles < (1ll << 24), ASQ_ERR_DIM, "%s: too many tiles", what);
+        // int8 groups run on v_mfma_i32_16x16x64_i8 (the L16 form of the kernel: asq_gemm_p16.h for why); ASQ_MMA=32 keeps the 32 x 32 x 32 form (A/B)
+        auto kfn = gemm_i8_p8<Epi, 0, true>;
+        if constexpr (kInt) {
+            if (!mma32_forced()) kfn = gemm_i8_p8<Epi, 0, true, true>;
+        }
+        bool g_offs = false;
+        if constexpr (kInt && Epi::kOutBytes == 2) g_offs = off.row != nullptr && !mma32_forced();
+        ASQ_REQUIRE(off.row == nullptr || (g_offs && K <= OFFSET_MAX_K && N % 4 == 0), ASQ_ERR_DIM, "%s: offset operands need int8 groups, 2-byte outputs, K <= 65536, N %% 4 == 0", what);
+        const int lds = g_offs ? P16_LDS_BYTES : P8_LDS_BYTES;
+        const hipError_t e = ensure_dynamic_lds((const void *)kfn, lds);
+        if (e != hipSuccess) {
+            asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+            return (int)e;
+        }
+        hipLaunchKernelGGL(kfn, dim3((unsigned)gg.tiles), dim3(512), lds, s, x, w, M, N, K, 0, (int)((N + 255) / 256), 1, goffs, ngroups, gg.tail_split ? (char *)ws_hdr : nullptr, epi,
+                           g_offs ? off : OffsetArgs{});
+        return asq_after_launch(s, what);
+    }
+    PlanInput in{M, N, K, aligned16, ws_hdr != nullptr, ws_bytes, off.row != nullptr};
+    if (in.offsets) {   // offset operands: gemm_i8_p16 only (the entry point has checked the shape: asq_offsets_supported)
+        ASQ_REQUIRE(kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4) && offsets_shape_ok(x, w, M, N, K), ASQ_ERR_DIM, "%s: offset operands need the 256 x 256 kernel (2- or 4-byte output, K %% 128 == 0, K <= 65536, N %% 4 == 0, aligned operands)", what);
+    }
+    if constexpr (kInt && Epi::kOutBytes == 2) in.out_rows16 = ((((uintptr_t)epi.out) & 15) == 0) && (epi.N * 2) % 16 == 0 && epi.N * 2 < (int64_t(1) << 24);
+    const GemmPlan plan = plan_gemm(epi_caps<Epi>(), in);
+    int rc = launch_part(plan.part[0], x, w, M, plan.part[0].n, K, epi, s, what, ws_hdr, ws, off);
+    if constexpr (HasColView<Epi>::value) {   // a tail peel's column remainder
+        const LaunchPlan &r = plan.part[1];
+        if (rc == ASQ_OK && plan.nparts == 2) rc = launch_part(r, x, w + r.n0 * K, M, r.n, K, epi.col_view(r.n0), s, what, ws_hdr, ws, off);
+    }
+    return rc;
 }
 
 template <class Epi>
@@ -1740,7 +1406,7 @@ int launch_gemm(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t 
         ASQ_REQUIRE(e == hipSuccess && magic == WS_MAGIC, ASQ_ERR_WORKSPACE, "%s: workspace header not initialised (asq_workspace_init)", what);
     }
     return launch_gemm_impl(x, w, M, N, K, epi, s, what, has ? ws : nullptr, has ? (char *)ws + WS_HEADER_BYTES : nullptr, has ? ws_bytes - WS_HEADER_BYTES : 0, goffs,
-                            ngroups, 0, off);
+                            ngroups, off);
 }
 
 // per-dtype instantiation units (asq_gemm_inst_*.hip)

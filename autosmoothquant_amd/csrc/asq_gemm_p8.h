@@ -49,7 +49,7 @@ constexpr int P8_LDS_BYTES = 2 * P8_STAGE;
 constexpr int P16_LDS_BYTES = P8_LDS_BYTES + 4096;   // gemm_i8_p16 on offset operands: + the tile's 256 row and 256 column pairs behind the ring
 // grouped launches (the scheduler at the top of gemm_i8_p8)
 constexpr int P8_GROUPED_SCAN_MAX = 64;     // groups a block may scan twice (tile total, then its own tile)
-constexpr int P8_CUS_PER_XCD = 32;          // MI355X: 256 CUs in 8 XCDs; one 128-KiB-LDS block per CU
+// (P8_CUS_PER_XCD = 32: asq_gemm_plan.h)
 constexpr int P8_TAIL_SPLIT_MAX = 8;        // K pieces of a tail tile
 #ifndef P8_FIX_BATCH
 #define P8_FIX_BATCH 8                      // 16-B loads per lane in flight while the last piece sums the others' images

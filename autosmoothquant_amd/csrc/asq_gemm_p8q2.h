@@ -17,7 +17,7 @@
 //   * tile t+2 is visible to the reads of L(t+1): A waits for its part before g = 2t, B before g = 2t+1; A reads after g = 2t+1, B after g = 2t+2;
 //   * the slot of tile t-1 is free when tile t+3 is issued into it: every wave waited for its fragments of t-1 at the top of its L(t-1), i.e. before
 //     g = 2t-2 (A) / g = 2t-1 (B); A issues after g = 2t-1, B after g = 2t.
-// Same operands, same exact integer sums, same epilogues as gemm_i8_p8q<Epi, false, true>: results are bit-identical.
+// Same operands, same exact integer sums, same epilogues as gemm_i8_p8q's former 16 x 16 x 64 form, which it replaced: results are bit-identical.
 #pragma once
 
 namespace asq {

@@ -34,8 +34,8 @@
 
 namespace asq {
 
-// (WS_HEADER_BYTES, WS_MAGIC, WS_MAX_GROUPS: asq_gemm_kernels.h, shared with the grouped launch of asq_gemm_p8.h)
-constexpr int WS_CB = 128;  // channels per group = 8 waves x 16
+// (WS_HEADER_BYTES, WS_MAX_GROUPS: asq_gemm_plan.h; WS_MAGIC: asq_gemm_kernels.h, shared with the grouped launch of asq_gemm_p8.h)
+// (WS_CB = 128 channels per group = 8 waves x 16: asq_gemm_plan.h)
 
 template <int MT> struct WsCfg {
     static constexpr int XI = 2 * MT;                      // X DMA instructions per unit (8 rows each)

@@ -26,6 +26,7 @@
 #include "../../autosmoothquant_amd/csrc/asq_gemm_inst_f16_row.hip"
 #include "../../autosmoothquant_amd/csrc/asq_gemm_inst_bf16_row.hip"
 #include "../../autosmoothquant_amd/csrc/asq_gemm.hip"
+#include "../../autosmoothquant_amd/csrc/asq_gemm_fq.hip"
 #include <vector>
 #include <map>
 #include <algorithm>

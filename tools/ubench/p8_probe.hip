@@ -10,6 +10,7 @@
 #include "../../autosmoothquant_amd/csrc/asq_gemm_inst_f16_row.hip"
 #include "../../autosmoothquant_amd/csrc/asq_gemm_inst_bf16_row.hip"
 #include "../../autosmoothquant_amd/csrc/asq_gemm.hip"
+#include "../../autosmoothquant_amd/csrc/asq_gemm_fq.hip"
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 
