@@ -117,7 +117,7 @@ int asq_quantize_act(const void *x, int x_dtype, int mode, float quant_scale,
 /* ---- N1: norm -> int8 fusion.  RMSNorm (bias == NULL; HF LlamaRMSNorm arithmetic) or LayerNorm
  * (bias != NULL; OPT) whose weight (and bias) already carry 1/input_scale (reference models/llama.py:27-37,
  * models/opt.py:20-29), fused with the activation quantiser of the linears that consume it -- the reference's
- * own unbuilt LayerNormQ (layers/nn/fused.py:10-15).  x, weight, bias share x_dtype; K <= 8192 (16-bit) / 4096 (f32).
+ * own unbuilt LayerNormQ (layers/nn/fused.py:10-15).  x, weight, bias share x_dtype; K <= 16384 (16-bit) / 8192 (f32).
  * per_token = 0: xq = int8(clamp(rne(y)));  1: s_row[m] = absmax(y)/127 (in x_dtype), xq = int8(clamp(rne(y / s_row))).
  * Every fp32 operation is fixed (per-thread accumulation order, butterfly reduction, 1/sqrt from one IEEE sqrt and
  * one IEEE division) and restated step by step in oracle/n1.py: the HIP result equals that restatement bit for bit.

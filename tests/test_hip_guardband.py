@@ -4,7 +4,8 @@ beyond its inputs.
 Each case runs one raw C-ABI call (pointers into a tests/guardband.py arena, the current stream) and checks
   1. the return code is ASQ_OK;
   2. every output region equals, bit for bit, what the ordinary ops.* call returns for the same operands in ordinary tensors
-     (those calls are what the rest of the suite ties to the oracle: every comparison here is equality);
+     (every comparison here is equality, between two launches of the same kernel: what ties those calls to the oracle is the rest of the suite -- at the
+     ladder lengths of this file tests/test_hip_row_ladders.py, at model sizes the test_hip_* file of each family);
   3. every guard is intact -- also the one behind a workspace of exactly asq_*_workspace_bytes(...) bytes;
   4. every input region (for a strided input: the whole buffer, the bytes between its rows included) is unchanged;
   5. the outputs are identical under the 0x7F and the 0xFF input flanks.
@@ -35,6 +36,7 @@ import torch
 
 import guardband as GB
 from autosmoothquant_amd import _lib as L
+from row_ladders import NORM, OFF_BLOCK, PT_BLOCK, SILU, WAVE_F8, WAVE_I8, ladder
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -177,18 +179,7 @@ def run_case(c):
 # =====================================================================================================================================
 # K ladders of the row kernels (asq_quant.hip / asq_fp8.hip): per tier its top, the first K of the next tier, a partial last 64-lane round
 # =====================================================================================================================================
-WAVE_I8 = (1, 2, 4, 6, 8, 10, 12, 16, 22, 24, 28)      # launch_rows_wave: nv = ceil(K / VEC / 64)
-WAVE_F8 = (1, 2, 4, 8, 12, 16, 22, 28)                 # launch_fp8_rows_wave
-
-
-def ladder(tiers, lanes, max_nvec, lo=0):
-    """K / VEC values: for each tier T of a `lanes`-wide ladder its top (lanes * T), one vector above it and one with a partial last round of 64 lanes"""
-    out = []
-    for t in tiers:
-        for nvec in (lanes * (t - 1) + (27 if lanes == 64 else 91), lanes * t, lanes * t + 1):
-            if lo < nvec <= max_nvec and nvec not in out:
-                out.append(nvec)
-    return out
+# (the tier tuples and ladder() live in tests/row_ladders.py, shared with tests/test_hip_row_ladders.py; tests/test_row_ladders_cpu.py ties them to the sources)
 
 
 def rows_for(i):
@@ -227,7 +218,7 @@ def _quantize_act(dt, mode, M, K, xq_skew=0, x_skew=0, off=False):
 for dt in FLOATS:
     v = VEC[dt]
     # per-token: the wave ladder, then quant_per_token_cached<8, 12, 20>, then the generic kernel (K / VEC > 5120)
-    ks = ladder(WAVE_I8, 64, 1793) + ladder((8, 12, 20), 256, 5121, lo=1793)
+    ks = ladder(WAVE_I8, 64, 1793) + ladder(PT_BLOCK, 256, 5121, lo=1793)
     for i, nvec in enumerate(ks):
         case("asq_quantize_act", f"pt-{NAME[dt]}-nvec{nvec}")(_quantize_act(dt, "per-token", rows_for(i), nvec * v, xq_skew=v))
     for M in ROWS:
@@ -244,7 +235,7 @@ for dt in FLOATS:
         case("asq_quantize_act", f"{mode}-{NAME[dt]}-unaligned-x")(_quantize_act(dt, mode, 3, 48, x_skew=esize(dt)))
     # offset images: wave ladder (per-tensor rows: up to 24 vectors per lane, per-token 28), then quant_rows_off<8, 20>
     for mode, top in (("per-token", 1792), ("per-tensor-round", 1536)):
-        ks = ladder(WAVE_I8, 64, top + 1) + ladder((8, 20), 256, 5120, lo=top + 1)
+        ks = ladder(WAVE_I8, 64, top + 1) + ladder(OFF_BLOCK, 256, 5120, lo=top + 1)
         for i, nvec in enumerate(ks):
             case("asq_quantize_act_off", f"{mode}-{NAME[dt]}-nvec{nvec}")(_quantize_act(dt, mode, rows_for(i + 2), nvec * v, xq_skew=v, off=True))
     for nvec in (27, 64, 1536, 1537, 2049, 5120):
@@ -254,7 +245,7 @@ for dt in FLOATS:
 
 
 # ---- the norm -> int8 family (norm_quant_cached<NV = 1, 2, 4, 8>: one block per row, K / VEC <= 2048) -------------------------------------
-NORM_KS = ladder((1, 2, 4, 8), 256, 2048)
+NORM_KS = ladder(NORM, 256, 2048)
 
 
 def _norm_quantize(entry, dt, M, K, ln, pt, inplace=False, xq_skew=None):
@@ -355,7 +346,7 @@ for dt in FLOATS:
 
 
 # ---- SiLU(gate) * up: int8 (silu_mul_quant_cached<2, 4, 6, 8>), e4m3 (silu_mul_quant_fp8_cached<2, 4, 6, 8>), floating (flat) --------------
-SILU_KS = ladder((2, 4, 6, 8), 256, 2048)
+SILU_KS = ladder(SILU, 256, 2048)
 
 
 def _silu_mul_quantize(entry, dt, M, K, pt, fast):

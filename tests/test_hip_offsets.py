@@ -66,9 +66,10 @@ def test_quantize_act_off_is_quantize_act_plus_row_offsets(dt, mode):
 @pytest.mark.parametrize("dt", ["f16", "bf16", "f32"])
 @pytest.mark.parametrize("mode", ["per-tensor-round", "per-tensor-div", "per-token"])
 def test_two_rows_per_wave_quantisers_against_the_oracle(dt, mode):
-    """>= 4096 rows of 4 / 6 / 8 / 10 / 12 sixty-four-lane vectors take the two-rows-per-wave kernel (second row's loads in flight behind the first row's arithmetic,
-    waits counted by hand): plain and image outputs against the oracle, with a row count that leaves the last waves without a second row and row lengths whose
-    last vector is partial (lanes past the row re-read its last vector)."""
+    """>= 4096 rows of 4 / 6 / 8 / 10 / 12 sixty-four-lane vectors through the one-wave-per-row kernel quant_rows_wave (loads in flight together, waits counted by
+    hand; the two-rows-per-wave form this test was written for was measured slower and dropped, csrc/asq_quant.hip): plain and image outputs against the oracle, with
+    row counts that leave the last 4-row block partly empty and row lengths whose last 64-lane round is partial (lanes past the row re-read its last vector).
+    Every tier of the ladder at its top, above it and with a partial round: tests/test_hip_row_ladders.py."""
     from autosmoothquant_amd import ops
     rng = np.random.default_rng(11)
     vec = 4 if dt == "f32" else 8

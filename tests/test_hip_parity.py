@@ -219,7 +219,7 @@ def test_gemm_unaligned_operands_take_generic_path(dev):
 
 @pytest.mark.parametrize("dt", ["f32", "f16", "bf16"])
 @pytest.mark.parametrize("shape", [(5, 64), (33, 320), (7, 4096), (3, 11008), (2, 20480), (4, 24584), (9, 77),
-                                   (1030, 512), (1500, 4096), (1025, 1000), (1026, 14336), (1100, 13312)])  # >= 1024 rows: wave-per-row kernel (the last two: 28 vectors per lane in fp16 / bf16)
+                                   (1030, 512), (1500, 4096), (1025, 1000), (1026, 14336), (1100, 13312)])  # per-token: the wave-per-row kernel takes every K / VEC <= 1792 whatever M (the last two: 28 vectors per lane in fp16 / bf16), longer rows quant_per_token_cached<8, 12, 20>, K = 77 (and 24584 in fp32) the generic kernel; every tier: tests/test_hip_row_ladders.py
 def test_quantize_act_vs_oracle(dt, shape, dev):
     from autosmoothquant_amd import ops
     M, K = shape
@@ -512,8 +512,9 @@ def test_forward_outputs_never_require_grad(dev):
 
 
 def test_large_shapes_with_4_byte_and_ragged_outputs(dev):
-    """>= 144 tiles of 256 x 256 with outputs gemm_i8_p16 does not carry (fp32, int32) go to p8's 16 x 16 x 64 mode, ragged edges to the bounded staged /
-    direct epilogues of that layout: int32 == torch._int_mm (an independent exact GEMM), fp32 / fp16 == the same fp32 operation sequence in torch."""
+    """>= 144 tiles of 256 x 256 with 4-byte outputs (fp32, int32): gemm_i8_p16 carries 2- and 4-byte outputs itself (plan_gemm hands only int8 outputs to p8's
+    16 x 16 x 64 mode), ragged edges go through its bounded staged / direct epilogues: int32 == torch._int_mm (an independent exact GEMM), fp32 / fp16 / bf16 == the
+    same fp32 operation sequence in torch."""
     from autosmoothquant_amd import ops
     for (M, N, K) in [(3072, 3072, 512), (3000, 3100, 384), (2900, 3330, 256)]:
         xq = torch.from_numpy(detrng.int8_uniform(210, M, (M, K))).to(dev)
