@@ -258,7 +258,9 @@ __global__ void __launch_bounds__(256, 1) gemm_i8_p4(const int8_t *__restrict__ 
     if (kRows && !(PROBE & 16) && staged && mw0 + 128 <= M && nw0 + 128 <= N && epi.N < (int64_t(1) << 27)) {
         if constexpr (kRows) epilogue_wave_rows<4, 4>(epi, [&](int in, int im) -> const v16i & { return acc[in][im]; }, mw0, nw0, lane, lds0 + wave * 32768);
     } else if (staged) {
-        p4_epilogue_rows(epi, [&](int in, int im) -> const v16i & { return acc[in][im]; }, mw0, nw0, lane, M, N, lds0 + wave * 16384);
+        // (inside this wave's own 32 KiB: an interior wave of the same block stages 32 KiB at wave * 32768 above, so wave * 16384 here let waves 2 / 3 of a
+        // block whose lower 128 rows are interior write over wave 1's images -- M % 256 in [128, 255]; found by tests/test_hip_gemm_extremes.py at 128 x 256 x 16384)
+        p4_epilogue_rows(epi, [&](int in, int im) -> const v16i & { return acc[in][im]; }, mw0, nw0, lane, M, N, lds0 + wave * 32768);
     } else {  // unaligned output / ragged row pitch: direct stores in the matrix-core layout, two 128 x 64 halves
         epilogue_wave<2, 4>(epi, [&](int in, int im) -> const v16i & { return acc[in][im]; }, [](int im) { return im * 32; }, mw0, nw0, lane, M, N);
         epilogue_wave<2, 4>(epi, [&](int in, int im) -> const v16i & { return acc[2 + in][im]; }, [](int im) { return im * 32; }, mw0, nw0 + 64, lane, M, N);

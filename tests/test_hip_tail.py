@@ -54,8 +54,10 @@ def test_tail_equals_plain_end(dt, shape):
     assert np.array_equal(got, ref)
 
 
-def test_tail_int8_extremes_and_wraparound():
-    """every operand at -128 / 127 (the largest accumulators of the int8 domain) through the TAIL kernel, on plain operands and on images"""
+def test_tail_int8_extremes():
+    """every operand at -128 or 127 with random signs (|acc| up to ~2^21: the largest PRODUCTS of the int8 domain, accumulators still exact in fp32; nothing wraps)
+    through an interior-tile launch of the 256 x 256 kernel, fp16 output with a scalar scale, against torch's exact int8 matmul.  Accumulators beyond 2^24 on every
+    kernel form: tests/test_hip_gemm_extremes.py"""
     from autosmoothquant_amd import ops
     M, N, K = 2304, 4096, 2048
     g = torch.Generator(device=DEV).manual_seed(11)
