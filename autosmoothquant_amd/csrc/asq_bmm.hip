@@ -15,8 +15,14 @@
 //   bmm_i8_m16   M <= 16 (decode): one 16-row MFMA tile, 32 output columns per block; each wave streams its share of the K steps of B straight into
 //                MFMA fragments with 16-B loads (no LDS for the operands, no 128-row padding), the four waves' partial sums meet in LDS.
 //   bmm_i8_sm128 the softmax kinds (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]): a block owns 128 rows of a batch and walks B twice; see below.
+// ASQ_BMM_B_KN on a plain kind: b is [batch, K, N] (N contiguous: V of P.V, a KV cache's layout) and is transposed on its way into the fragments:
+//   bmm_i8_t128<KIND, true> ("t128kn")  t128 with another way of B into LDS: a thread holds 4 consecutive k rows of one 16-column chunk, transposes the four 4 x 4
+//                byte blocks with v_perm_b32 and writes 16 dwords (4 consecutive k of one n) into the [n row][k] image the fragment reads expect.
+//   bmm_i8_m16kn ("m16kn", M <= 16)     m16 over 64 columns per block: a lane loads dwords (4 columns) of its 16 k rows and transposes them into 4 MFMA operands.
 // Loads: unguarded 16-B loads when K % 16 == 0 and the operands are 16-B aligned, otherwise load16_guarded's zero-filled byte path (any K, any
-// alignment).  Every offset is 64-bit.  No workspace, no split-K across workgroups.
+// alignment); the KN kinds also want N % 16 == 0 for the unguarded loads of b (its row pitch).  The kernels take ONE such flag, so a KN call with
+// N % 16 != 0 reads a byte-wise too although only b needs it: correct, slower on such shapes (the plain kernels' signature is kept as it was).
+// Every offset is 64-bit.  No workspace, no split-K across workgroups.
 #include "asq_gemm_kernels.h"
 
 namespace asq {
@@ -73,10 +79,23 @@ template <int EB> __device__ __forceinline__ void bmm_store_chunk(void *out, int
     }
 }
 
+// 4 x 4 byte transpose: byte c of r[i] -> byte i of d[c]  (r[i] = 4 consecutive n of k row i  ->  d[c] = 4 consecutive k of column c)
+__device__ __forceinline__ void bmm_transpose4(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t (&d)[4])
+{
+    const uint32_t t0 = __builtin_amdgcn_perm(r1, r0, 0x05010400u), t1 = __builtin_amdgcn_perm(r1, r0, 0x07030602u);   // r0.b0 r1.b0 r0.b1 r1.b1 | .b2 .b3
+    const uint32_t u0 = __builtin_amdgcn_perm(r3, r2, 0x05010400u), u1 = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
+    d[0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u), d[1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
+    d[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u), d[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
+}
+
 constexpr int BMM_TM = 128, BMM_TN = 128, BMM_TK = 128;
 
-template <int KIND>
-__global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 ? 3 : 2) bmm_i8_t128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
+// KN: b is [batch, K, N].  A K step of it is [128 k][128 n]: thread tid holds rows 4 kg .. 4 kg + 3 (kg = tid >> 3) of the 16-column chunk nc = tid & 7, so a wave's
+// load covers 8 rows of 128 contiguous bytes.  Its B image is [n row][16-B chunks of k] with chunk index ^= ((row >> 1) & 7) ^ (row >> 4): the second term is constant
+// over the 16 rows of a fragment read (the reads stay conflict-free) and spreads the dword writes of a 32-lane half -- 8 nc x 4 (kg & 3), one kg >> 2 -- over all 32 banks.
+// The transpose's registers do not fit the int8 kind's 3 blocks per CU without spilling: KN runs 2 blocks per CU for every kind.
+template <int KIND, bool KN = false>
+__global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8_t128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
                                                    int64_t K, int64_t tiles_m, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec)
 {
     constexpr int EB = BmmOut<KIND>::kBytes, RB = BMM_TN * EB, NC = RB / 16;   // staging image: 64 rows of RB bytes = NC 16-B chunks
@@ -100,7 +119,8 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 ? 3 : 2) bmm_i8_t128(c
             for (int i = 0; i < 4; ++i) {
                 const int c = tid + 256 * i, row = c >> 3, ch = c & 7;
                 px[i] = load16_guarded(ab, K, m0 + row, M, k0 + ch * 16, K, fast);
-                pw[i] = load16_guarded(bb, K, n0 + row, N, k0 + ch * 16, K, fast);
+                if constexpr (KN) pw[i] = load16_guarded(bb, N, k0 + 4 * (tid >> 3) + i, K, n0 + 16 * (tid & 7), N, fast);
+                else pw[i] = load16_guarded(bb, K, n0 + row, N, k0 + ch * 16, K, fast);
             }
         };
         v4i acc[4][4];   // [m tile][n tile] of the wave's 64 x 64
@@ -116,7 +136,18 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 ? 3 : 2) bmm_i8_t128(c
                 const int c = tid + 256 * i, row = c >> 3, ch = c & 7;
                 const int off = row * BMM_TK + ((ch ^ ((row >> 1) & 7)) << 4);
                 *(v4i *)(xs + off) = px[i];
-                *(v4i *)(ws + off) = pw[i];
+                if constexpr (!KN) *(v4i *)(ws + off) = pw[i];
+            }
+            if constexpr (KN) {
+                const int nc = tid & 7, kg = tid >> 3, x = (kg >> 2) ^ nc;
+                char *const wp = ws + nc * 16 * BMM_TK + (kg & 3) * 4;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t d[4];
+                    bmm_transpose4(pw[0][w], pw[1][w], pw[2][w], pw[3][w], d);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) *(uint32_t *)(wp + (4 * w + e) * BMM_TK + ((x ^ (2 * w + (e >> 1))) << 4)) = d[e];   // row 16 nc + 4 w + e
+                }
             }
             __syncthreads();
             if (s + 1 < nsteps) load((s + 1) * BMM_TK);   // in flight during this step's matrix work
@@ -128,7 +159,7 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 ? 3 : 2) bmm_i8_t128(c
                 for (int i = 0; i < 4; ++i) {
                     const int rx = wm * 64 + i * 16 + t16, rw = wn * 64 + i * 16 + t16;
                     fx[i] = *(const v4i *)(xs + rx * BMM_TK + ((ch ^ ((rx >> 1) & 7)) << 4));
-                    fw[i] = *(const v4i *)(ws + rw * BMM_TK + ((ch ^ ((rw >> 1) & 7)) << 4));
+                    fw[i] = *(const v4i *)(ws + rw * BMM_TK + ((ch ^ ((rw >> 1) & 7) ^ (KN ? rw >> 4 : 0)) << 4));
                 }
                 // lane: column m = t16 of the m tile, rows n = 4 q16 .. + 3 of the n tile (the 16 x 16 layout of epilogue_wave16)
 #pragma unroll
@@ -206,6 +237,89 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
             const int j = wave;
             const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
             const int64_t m = t16, n = n0 + 16 * j + 4 * q16;
+            if (m < M && n < N) {
+                const int64_t off = bt * M * N + m * N + n;
+                if constexpr (EB == 4) {
+                    const v4i v = bmm_pack16<KIND>(s, alpha);
+                    if (vec4 && n + 4 <= N) {
+                        *(v4i *)((int32_t *)out + off) = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (n + e < N) ((int32_t *)out)[off + e] = v[e];
+                    }
+                } else {
+                    const uint32_t v = bmm_pack4<KIND>(s, alpha);
+                    if (vec4 && n + 4 <= N) {
+                        *(uint32_t *)((int8_t *)out + off) = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (n + e < N) ((int8_t *)out)[off + e] = (int8_t)(v >> (8 * e));
+                    }
+                }
+            }
+        }
+        __syncthreads();   // red is rewritten by the next tile of a grid-stride loop
+    }
+}
+
+// M <= 16 with b as [batch, K, N]: 64 output columns per block.  In a K step lane (t16, q16) loads the dword b[k0 + 16 q16 + r][n0 + 4 t16 .. + 3] of each of its
+// 16 rows r and transposes them into four B operands, one per column it holds: MFMA e sees column n0 + 4 t + e in its slot t.  Its accumulator register `reg` of
+// lane (t16, q16) is then row t16, column n0 + 4 (4 q16 + reg) + e, so the four MFMAs' registers `reg` are 4 consecutive columns: red[wave][reg][lane].
+constexpr int BMM_KN_TN = 64;
+
+__device__ __forceinline__ uint32_t load4_kn(const int8_t *base, int64_t N, int64_t k, int64_t K, int64_t n, bool fast)
+{
+    if (k >= K || n >= N) return 0;
+    const int8_t *p = base + k * N + n;
+    if (fast) return *(const uint32_t *)p;   // N % 16 == 0, n % 4 == 0, base 16-B aligned
+    uint32_t w = 0;
+    for (int i = 0; i < 4; ++i)
+        if (n + i < N) w |= (uint32_t)(uint8_t)p[i] << (8 * i);
+    return w;
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
+                                                    int64_t K, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec4)
+{
+    constexpr int EB = BmmOut<KIND>::kBytes;
+    __shared__ v4i red[4][4][64];   // each wave's partial sums: [wave][accumulator register][lane], the 4 ints are 4 consecutive columns
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t16 = lane & 15, q16 = lane >> 4;
+    const int64_t nks = (K + 63) / 64;
+
+    for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
+        const int64_t bt = id / tiles_n, n0 = (id - bt * tiles_n) * BMM_KN_TN;
+        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * K * N;
+        v4i acc[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = (v4i){0, 0, 0, 0};
+        for (int64_t ks = wave; ks < nks; ks += 4) {
+            const int64_t k = ks * 64 + q16 * 16;
+            const v4i fx = load16_guarded(ab, K, t16, M, k, K, fast);
+            uint32_t rows[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rows[r] = load4_kn(bb, N, k + r, K, n0 + 4 * t16, fast);
+            v4i fw[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                uint32_t d[4];
+                bmm_transpose4(rows[4 * g], rows[4 * g + 1], rows[4 * g + 2], rows[4 * g + 3], d);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) fw[e][g] = (int)d[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = MmaI8x16::mma(fw[e], fx, acc[e]);
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) red[wave][reg][lane] = (v4i){acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]};
+        __syncthreads();
+        {   // wave j finishes register j of every lane: exact int32 sum of the four partials, then the epilogue
+            const int j = wave;
+            const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
+            const int64_t m = t16, n = n0 + 16 * q16 + 4 * j;
             if (m < M && n < N) {
                 const int64_t off = bt * M * N + m * N + n;
                 if constexpr (EB == 4) {
@@ -483,6 +597,24 @@ static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch
     return asq_after_launch(s, "asq_bmm_i8");
 }
 
+template <int KIND>   // b is [batch, K, N]
+static int launch_bmm_kn(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    constexpr int EB = BmmOut<KIND>::kBytes;
+    const bool fast = (K % 16 == 0) && (N % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
+    if (bmm_narrow(M)) {
+        const int64_t tiles_n = (N + BMM_KN_TN - 1) / BMM_KN_TN, total = batch * tiles_n;
+        const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
+        hipLaunchKernelGGL((bmm_i8_m16kn<KIND>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, alpha, fast, vec4);
+    } else {
+        const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
+        const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
+        hipLaunchKernelGGL((bmm_i8_t128<KIND, true>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, alpha,
+                           fast, vec);
+    }
+    return asq_after_launch(s, "asq_bmm_i8");
+}
+
 static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
 {
     const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0), vec = (N % 16 == 0) && (((uintptr_t)out & 15) == 0);
@@ -497,6 +629,8 @@ static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int
 
 static inline bool bmm_softmax_kind(int k) { return k == (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX) || k == (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL); }
 
+static inline bool bmm_kn_kind(int k) { return k >= (ASQ_BMM_B_KN | ASQ_BMM_S32) && k <= (ASQ_BMM_B_KN | ASQ_BMM_S8); }
+
 static inline bool bmm_mul(int64_t x, int64_t y, int64_t &r) { return !__builtin_mul_overflow(x, y, &r); }
 
 }  // namespace asq
@@ -507,6 +641,7 @@ extern "C" const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, 
 {
     if (batch <= 0 || M <= 0 || N <= 0 || K < 0) return "none";
     if (bmm_softmax_kind(out_kind)) return "sm128";
+    if (bmm_kn_kind(out_kind)) return bmm_narrow(M) ? "m16kn" : "t128kn";
     if (out_kind < ASQ_BMM_S32 || out_kind > ASQ_BMM_S8) return "none";
     return bmm_narrow(M) ? "m16" : "t128";
 }
@@ -520,14 +655,17 @@ extern "C" int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_k
     ASQ_REQUIRE(bmm_mul(M, N, mn) && bmm_mul(batch, mn, bmn) && bmm_mul(bmn, 4, bytes) && bmm_mul(M, K, mk) && bmm_mul(batch, mk, bmk) && bmm_mul(N, K, nk) &&
                     bmm_mul(batch, nk, bnk),
                 ASQ_ERR_DIM, "asq_bmm_i8: size overflows 64 bits (batch=%lld M=%lld N=%lld K=%lld)", (long long)batch, (long long)M, (long long)N, (long long)K);
-    ASQ_REQUIRE(out_kind == ASQ_BMM_S32 || out_kind == ASQ_BMM_F32 || out_kind == ASQ_BMM_S8 || bmm_softmax_kind(out_kind), ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
+    ASQ_REQUIRE(out_kind == ASQ_BMM_S32 || out_kind == ASQ_BMM_F32 || out_kind == ASQ_BMM_S8 || bmm_softmax_kind(out_kind) || bmm_kn_kind(out_kind), ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
     if (bmn == 0) return ASQ_OK;
     ASQ_REQUIRE(out != nullptr, ASQ_ERR_NULL, "asq_bmm_i8: NULL out");
     ASQ_REQUIRE(K == 0 || (a != nullptr && b != nullptr), ASQ_ERR_NULL, "asq_bmm_i8: NULL a / b");
-    ASQ_REQUIRE(out_kind == ASQ_BMM_S8 || bmm_softmax_kind(out_kind) || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
+    ASQ_REQUIRE((out_kind & ~ASQ_BMM_B_KN) == ASQ_BMM_S8 || bmm_softmax_kind(out_kind) || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
     hipStream_t s = (hipStream_t)stream;
     if (bmm_softmax_kind(out_kind)) return launch_bmm_softmax(a, b, (int8_t *)out, batch, M, N, K, alpha, (out_kind & ASQ_BMM_CAUSAL) != 0, s);
     switch (out_kind) {
+    case ASQ_BMM_B_KN | ASQ_BMM_S32: return launch_bmm_kn<ASQ_BMM_S32>(a, b, out, batch, M, N, K, alpha, s);
+    case ASQ_BMM_B_KN | ASQ_BMM_F32: return launch_bmm_kn<ASQ_BMM_F32>(a, b, out, batch, M, N, K, alpha, s);
+    case ASQ_BMM_B_KN | ASQ_BMM_S8: return launch_bmm_kn<ASQ_BMM_S8>(a, b, out, batch, M, N, K, alpha, s);
     case ASQ_BMM_S32: return launch_bmm<ASQ_BMM_S32>(a, b, out, batch, M, N, K, alpha, s);
     case ASQ_BMM_F32: return launch_bmm<ASQ_BMM_F32>(a, b, out, batch, M, N, K, alpha, s);
     default: return launch_bmm<ASQ_BMM_S8>(a, b, out, batch, M, N, K, alpha, s);

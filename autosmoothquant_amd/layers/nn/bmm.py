@@ -8,6 +8,8 @@ Checkpoint contract (as the reference): BMM_S8T_S8N_S8T and BMM_S8T_S8N_F32T hol
 a 0-dim tensor whose dtype follows the module's, so ``.half()`` rounds it to fp16); BMM_S8T_S8N_S32T holds none.
 BMM_S8T_S8N_SOFTMAX_S8T (not in the reference: QK^T with the softmax -> int8 epilogue fused, the P that BMM_S8T_S8N_S8T
 consumes) holds ``a`` as its siblings; ``causal`` is a plain attribute and not part of the state dict.
+BMM_S8T_S8T_S8T / _F32T / _S32T (not in the reference) take b row-major, [B, K, N] -- V of P.V as it is stored -- and are otherwise their S8N siblings:
+the same buffer, ``from_scale`` and epilogue, one launch of asq_bmm_i8 with ASQ_BMM_B_KN and no transposed copy.
 ``a`` lives on the HOST after any ``.cuda()/.to()``, so ``forward`` reads it without synchronising the device; the
 kernel receives fp32(a.item()), which is the reference's ``float alpha`` argument."""
 import torch
@@ -90,3 +92,32 @@ class BMM_S8T_S8N_S32T(torch.nn.Module):
     def forward(self, a, b):
         # a: [B, M, K] int8, b: [B, N, K] int8 -> [B, M, N] int32 = a . b^T (exact)
         return bmm_s8t_s8n_s32t(a, b)
+
+
+class BMM_S8T_S8T_S8T(_ScaledBMM):
+    def forward(self, a, b):
+        # a: [B, M, K] int8, b: [B, K, N] int8 -> [B, M, N] int8 = sat_i8(rne(alpha * (a . b)))
+        return ops.bmm_i8_kn(a, b, torch.int8, self._alpha())
+
+    @staticmethod
+    def from_scale(a_scale, b_scale, output_scale):
+        return BMM_S8T_S8T_S8T._with_alpha(a_scale * b_scale / output_scale)
+
+
+class BMM_S8T_S8T_F32T(_ScaledBMM):
+    def forward(self, a, b):
+        # a: [B, M, K] int8, b: [B, K, N] int8 -> [B, M, N] float32 = alpha * float(a . b)
+        return ops.bmm_i8_kn(a, b, torch.float32, self._alpha())
+
+    @staticmethod
+    def from_scale(a_scale, b_scale):
+        return BMM_S8T_S8T_F32T._with_alpha(a_scale * b_scale)
+
+
+class BMM_S8T_S8T_S32T(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, a, b):
+        # a: [B, M, K] int8, b: [B, K, N] int8 -> [B, M, N] int32 = a . b (exact)
+        return ops.bmm_i8_kn(a, b, torch.int32)

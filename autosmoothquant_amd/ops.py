@@ -962,6 +962,29 @@ def bmm_i8(a, b, out_kind, alpha=1.0):
     return out
 
 
+def bmm_i8_kn(a, b, out_kind, alpha=1.0):
+    """Batched int8 A . B with b row-major (asq_bmm_i8 with ASQ_BMM_B_KN): a int8 [B, M, K], b int8 [B, K, N] -> a new [B, M, N] tensor on the current
+    stream, bit-identical to bmm_i8(a, b.transpose(1, 2).contiguous(), out_kind, alpha) without the copy.  out_kind: as bmm_i8 (a dtype or a plain
+    ASQ_BMM_S32 / _F32 / _S8 code); ASQ_BMM_B_KN may be set on a code and is implied."""
+    _dev(a, "a"), _dev(b, "b")
+    if a.dtype != torch.int8 or b.dtype != torch.int8:
+        raise RuntimeError(f"expected int8 a and b, got {a.dtype} and {b.dtype}")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[1]:
+        raise ValueError(f"shape mismatch: a {tuple(a.shape)} must be [B, M, K] and b {tuple(b.shape)} [B, K, N]")
+    kind = _BMM_KIND.get(out_kind, out_kind) if isinstance(out_kind, torch.dtype) else out_kind
+    if isinstance(kind, int):
+        kind &= ~L.ASQ_BMM_B_KN   # 128 .. 130 name the same three kinds
+    if kind not in _BMM_DTYPE:
+        raise ValueError(f"out_kind must be torch.int32, torch.float32 or torch.int8 (or an ASQ_BMM_* code), got {out_kind!r}")
+    dev = _same_device(a, b)
+    B, M, K = a.shape
+    N = b.shape[2]
+    out = torch.empty((B, M, N), dtype=_BMM_DTYPE[kind], device=dev)
+    with _on(dev):
+        L.check(L.lib().asq_bmm_i8(a.data_ptr(), b.data_ptr(), out.data_ptr(), kind | L.ASQ_BMM_B_KN, B, M, N, K, float(alpha), _stream(a)), "asq_bmm_i8")
+    return out
+
+
 def bmm_i8_softmax_q8(a, b, alpha, causal=False):
     """QK^T with the softmax -> int8 epilogue fused (asq_bmm_i8 with ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]): a int8 [B, M, K], b int8 [B, N, K]
     -> a new int8 [B, M, N] = rne(127 * softmax(alpha * (a . b^T), -1)) on the current stream, values 0 .. 127; the fp32 scores never reach memory.

@@ -399,7 +399,7 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
 #define ASQ_BMM_F32 1 /* bmm_s8t_s8n_f32t: out float = alpha * float(acc)            */
 #define ASQ_BMM_S8 2  /* bmm_s8t_s8n_s8t : out int8  = sat_i8(rne(alpha*float(acc))) */
 /* out_kind is a base kind in the low bits plus flags.  The valid values are 0, 1, 2, ASQ_BMM_S8 | ASQ_BMM_SOFTMAX (18) and
- * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50); every other value is ASQ_ERR_DTYPE / "none".
+ * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50), and ASQ_BMM_B_KN | {0, 1, 2} (128, 129, 130); every other value is ASQ_ERR_DTYPE / "none".
  *
  * The softmax kinds turn QK^T into the int8 probabilities that P.V consumes (asq_bmm_i8(p, vT, ASQ_BMM_S8) with alpha = v_scale / (127 * out_scale))
  * without the fp32 scores ever reaching memory.  out is int8 [batch, M, N]; per batch i and row m
@@ -417,6 +417,14 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
  * store).  There is no version bump for these kinds: probe with asq_bmm_kernel_name(batch, M, N, K, 18) != "none"; an older library answers "none". */
 #define ASQ_BMM_SOFTMAX 0x10 /* with ASQ_BMM_S8 only: row softmax of alpha * acc, then int8(rne(127 p)) */
 #define ASQ_BMM_CAUSAL 0x20  /* with ASQ_BMM_SOFTMAX only: key n is visible to query m iff n <= m + (N - M) */
+/* ASQ_BMM_B_KN, with ASQ_BMM_S32 / _F32 / _S8 only (not with the softmax flags): b is int8 [batch, K, N], dense (N contiguous: V of P.V as it is stored, the
+ * layout of a KV cache), and  acc[i, m, n] = sum_k a[i, m, k] * b[i, k, n];  the epilogue is the base kind's.  Every output element equals the base kind
+ * called on the transposed copy of b, bit for bit.  Everything else is as the base kind has it: any batch, M, N, K >= 0 and any alignment of a / b / out
+ * (N % 16 == 0 and K % 16 == 0 with 16-B aligned a and b take the unguarded load path), K = 0, the empty output, the argument rules and their order, no
+ * workspace, determinism and batch independence.  asq_bmm_kernel_name answers "m16kn" (M <= 16: 64 columns per block, b transposed in registers) and
+ * "t128kn" (the 128 x 128 tiles of "t128"; b is transposed on its way into LDS).  No version bump: probe with
+ * asq_bmm_kernel_name(batch, M, N, K, 130) != "none"; an older library answers "none". */
+#define ASQ_BMM_B_KN 0x80
 int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind,
                int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream);
 const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind);
