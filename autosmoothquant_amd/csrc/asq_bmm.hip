@@ -23,6 +23,9 @@
 // alignment); the KN kinds also want N % 16 == 0 for the unguarded loads of b (its row pitch).  The kernels take ONE such flag, so a KN call with
 // N % 16 != 0 reads a byte-wise too although only b needs it: correct, slower on such shapes (the plain kernels' signature is kept as it was).
 // Every offset is 64-bit.  No workspace, no split-K across workgroups.
+// What the kernels share is stated once: bmm_tile_off (the swizzled operand image of t128 / sm128), bmm_mma_step (a K step's fragment reads and 16 MFMAs),
+// bmm_stage_off (the output images), bmm_store4 (the finish of m16 / m16kn); on the host bmm_decode (out_kind) and launch_bmm<KIND, KN>.  The tile puts of
+// t128 and sm128 and the K loops of m16 and m16kn stay apart: shared, they would branch on their caller in every line.
 #include "asq_gemm_kernels.h"
 
 namespace asq {
@@ -79,6 +82,31 @@ template <int EB> __device__ __forceinline__ void bmm_store_chunk(void *out, int
     }
 }
 
+// The finish of the narrow kernels: the lane's 4 sums (row fixed, columns n .. n + 3, the first at element offset `off`) as one vector store when `vec4`
+// (N % 4 == 0 and out aligned to 4 elements) and all four are in range, otherwise up to 4 guarded scalar stores.
+template <int KIND> __device__ __forceinline__ void bmm_store4(void *out, int64_t off, const v4i &sum, int64_t n, int64_t N, float alpha, bool vec4)
+{
+    if constexpr (BmmOut<KIND>::kBytes == 4) {
+        const v4i v = bmm_pack16<KIND>(sum, alpha);
+        if (vec4 && n + 4 <= N) {
+            *(v4i *)((int32_t *)out + off) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (n + e < N) ((int32_t *)out)[off + e] = v[e];
+        }
+    } else {
+        const uint32_t v = bmm_pack4<KIND>(sum, alpha);
+        if (vec4 && n + 4 <= N) {
+            *(uint32_t *)((int8_t *)out + off) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (n + e < N) ((int8_t *)out)[off + e] = (int8_t)(v >> (8 * e));
+        }
+    }
+}
+
 // 4 x 4 byte transpose: byte c of r[i] -> byte i of d[c]  (r[i] = 4 consecutive n of k row i  ->  d[c] = 4 consecutive k of column c)
 __device__ __forceinline__ void bmm_transpose4(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t (&d)[4])
 {
@@ -89,6 +117,34 @@ __device__ __forceinline__ void bmm_transpose4(uint32_t r0, uint32_t r1, uint32_
 }
 
 constexpr int BMM_TM = 128, BMM_TN = 128, BMM_TK = 128;
+
+// The operand image of t128 and sm128: a K step of an operand is [128 rows][128 B], and 16-B chunk `chunk` of row `row` lies at chunk index
+// chunk ^ ((row >> 1) & 7): conflict-free fragment reads (the image of gemm_i8_p4x16).  The KN image of B passes chunk ^ (row >> 4).
+__device__ __forceinline__ int bmm_tile_off(int row, int chunk) { return row * BMM_TK + ((chunk ^ ((row >> 1) & 7)) << 4); }
+
+// The output images (t128's staging image, sm128's int8 image): rows of RB bytes, 16-B chunk c of image row ir is stored at c ^ (ir & (RB / 16 - 1)).
+template <int RB> __device__ __forceinline__ int bmm_stage_off(int ir, int c) { return ir * RB + ((c ^ (ir & (RB / 16 - 1))) << 4); }
+
+// A K step's matrix work of a wave's 64 x 64: the fragments of both tiles, then 4 x 4 MFMAs per half step.  rx / rw: the lane's row in the first 16-row
+// tile of the wave's A / B rows (wm * 64 + t16, wn * 64 + t16).  acc[i][j] of a lane: row t16 of m tile i, columns 4 q16 .. + 3 of n tile j (the MFMA
+// itself sees column m = t16, rows n = 4 q16 .. + 3: the 16 x 16 layout of epilogue_wave16).
+template <bool KN> __device__ __forceinline__ void bmm_mma_step(const char *xs, const char *ws, int rx, int rw, int q16, v4i (&acc)[4][4])
+{
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const int ch = kk * 4 + q16;
+        v4i fx[4], fw[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            fx[i] = *(const v4i *)(xs + bmm_tile_off(rx + i * 16, ch));
+            fw[i] = *(const v4i *)(ws + bmm_tile_off(rw + i * 16, KN ? ch ^ ((rw + i * 16) >> 4) : ch));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = MmaI8x16::mma(fw[j], fx[i], acc[i][j]);
+    }
+}
 
 // KN: b is [batch, K, N].  A K step of it is [128 k][128 n]: thread tid holds rows 4 kg .. 4 kg + 3 (kg = tid >> 3) of the 16-column chunk nc = tid & 7, so a wave's
 // load covers 8 rows of 128 contiguous bytes.  Its B image is [n row][16-B chunks of k] with chunk index ^= ((row >> 1) & 7) ^ (row >> 4): the second term is constant
@@ -111,8 +167,7 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
         const int64_t m0 = (r / tiles_n) * BMM_TM, n0 = (r % tiles_n) * BMM_TN;
         const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
 
-        // K step = [128 rows][128 B] of each operand; thread tid moves chunks tid + 256 i (row = chunk >> 3, 16-B column = chunk & 7).
-        // LDS chunk index ^= (row >> 1) & 7: conflict-free fragment reads (the image of gemm_i8_p4x16).
+        // K step = [128 rows][128 B] of each operand; thread tid moves chunks tid + 256 i (row = chunk >> 3, 16-B column = chunk & 7) into bmm_tile_off's image.
         v4i px[4], pw[4];
         auto load = [&](int64_t k0) {
 #pragma unroll
@@ -133,12 +188,13 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
             __syncthreads();   // the previous step's fragments have been read
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int c = tid + 256 * i, row = c >> 3, ch = c & 7;
-                const int off = row * BMM_TK + ((ch ^ ((row >> 1) & 7)) << 4);
+                const int c = tid + 256 * i, off = bmm_tile_off(c >> 3, c & 7);
                 *(v4i *)(xs + off) = px[i];
                 if constexpr (!KN) *(v4i *)(ws + off) = pw[i];
             }
             if constexpr (KN) {
+                // d[e] is dword kg & 3 of chunk kg >> 2 of row = 16 nc + 4 w + e.  Its offset is bmm_tile_off(row, (kg >> 2) ^ (row >> 4)) + 4 (kg & 3) with
+                // row >> 4 = nc and (row >> 1) & 7 = 2 w + (e >> 1) folded by hand.
                 const int nc = tid & 7, kg = tid >> 3, x = (kg >> 2) ^ nc;
                 char *const wp = ws + nc * 16 * BMM_TK + (kg & 3) * 4;
 #pragma unroll
@@ -151,22 +207,7 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
             }
             __syncthreads();
             if (s + 1 < nsteps) load((s + 1) * BMM_TK);   // in flight during this step's matrix work
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int ch = kk * 4 + q16;
-                v4i fx[4], fw[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int rx = wm * 64 + i * 16 + t16, rw = wn * 64 + i * 16 + t16;
-                    fx[i] = *(const v4i *)(xs + rx * BMM_TK + ((ch ^ ((rx >> 1) & 7)) << 4));
-                    fw[i] = *(const v4i *)(ws + rw * BMM_TK + ((ch ^ ((rw >> 1) & 7) ^ (KN ? rw >> 4 : 0)) << 4));
-                }
-                // lane: column m = t16 of the m tile, rows n = 4 q16 .. + 3 of the n tile (the 16 x 16 layout of epilogue_wave16)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = MmaI8x16::mma(fw[j], fx[i], acc[i][j]);
-            }
+            bmm_mma_step<KN>(xs, ws, wm * 64 + t16, wn * 64 + t16, q16, acc);
         }
         __syncthreads();   // the operand tiles are dead: the staging image takes their place
 
@@ -180,20 +221,15 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
                 const int im = 2 * p + ii, ir = wm * 32 + ii * 16 + t16;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if constexpr (EB == 4) {
-                        const int c = wn * 16 + j * 4 + q16;
-                        *(v4i *)(lds + ir * RB + ((c ^ (ir & (NC - 1))) << 4)) = bmm_pack16<KIND>(acc[im][j], alpha);
-                    } else {
-                        const int c = wn * 4 + j;
-                        *(uint32_t *)(lds + ir * RB + ((c ^ (ir & (NC - 1))) << 4) + 4 * q16) = bmm_pack4<KIND>(acc[im][j], alpha);
-                    }
+                    if constexpr (EB == 4) *(v4i *)(lds + bmm_stage_off<RB>(ir, wn * 16 + j * 4 + q16)) = bmm_pack16<KIND>(acc[im][j], alpha);
+                    else *(uint32_t *)(lds + bmm_stage_off<RB>(ir, wn * 4 + j) + 4 * q16) = bmm_pack4<KIND>(acc[im][j], alpha);
                 }
             }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < 64 * NC / 256; ++i) {
                 const int idx = tid + 256 * i, ir = idx / NC, c = idx % NC;
-                const v4i v = *(const v4i *)(lds + ir * RB + ((c ^ (ir & (NC - 1))) << 4));
+                const v4i v = *(const v4i *)(lds + bmm_stage_off<RB>(ir, c));
                 const int64_t m = m0 + (ir >> 5) * 64 + 32 * p + (ir & 31), n = n0 + c * (16 / EB);
                 if (m < M && n < N) bmm_store_chunk<EB>(out, obase + m * N + n, v, N - n, vec);
             }
@@ -208,7 +244,6 @@ template <int KIND>
 __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
                                                   int64_t K, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec4)
 {
-    constexpr int EB = BmmOut<KIND>::kBytes;
     __shared__ v4i red[4][BMM_NT][64];   // each wave's partial sums, lane-linear
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int t16 = lane & 15, q16 = lane >> 4;
@@ -237,28 +272,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
             const int j = wave;
             const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
             const int64_t m = t16, n = n0 + 16 * j + 4 * q16;
-            if (m < M && n < N) {
-                const int64_t off = bt * M * N + m * N + n;
-                if constexpr (EB == 4) {
-                    const v4i v = bmm_pack16<KIND>(s, alpha);
-                    if (vec4 && n + 4 <= N) {
-                        *(v4i *)((int32_t *)out + off) = v;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (n + e < N) ((int32_t *)out)[off + e] = v[e];
-                    }
-                } else {
-                    const uint32_t v = bmm_pack4<KIND>(s, alpha);
-                    if (vec4 && n + 4 <= N) {
-                        *(uint32_t *)((int8_t *)out + off) = v;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (n + e < N) ((int8_t *)out)[off + e] = (int8_t)(v >> (8 * e));
-                    }
-                }
-            }
+            if (m < M && n < N) bmm_store4<KIND>(out, bt * M * N + m * N + n, s, n, N, alpha, vec4);
         }
         __syncthreads();   // red is rewritten by the next tile of a grid-stride loop
     }
@@ -284,7 +298,6 @@ template <int KIND>
 __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
                                                     int64_t K, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec4)
 {
-    constexpr int EB = BmmOut<KIND>::kBytes;
     __shared__ v4i red[4][4][64];   // each wave's partial sums: [wave][accumulator register][lane], the 4 ints are 4 consecutive columns
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int t16 = lane & 15, q16 = lane >> 4;
@@ -320,28 +333,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
             const int j = wave;
             const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
             const int64_t m = t16, n = n0 + 16 * q16 + 4 * j;
-            if (m < M && n < N) {
-                const int64_t off = bt * M * N + m * N + n;
-                if constexpr (EB == 4) {
-                    const v4i v = bmm_pack16<KIND>(s, alpha);
-                    if (vec4 && n + 4 <= N) {
-                        *(v4i *)((int32_t *)out + off) = v;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (n + e < N) ((int32_t *)out)[off + e] = v[e];
-                    }
-                } else {
-                    const uint32_t v = bmm_pack4<KIND>(s, alpha);
-                    if (vec4 && n + 4 <= N) {
-                        *(uint32_t *)((int8_t *)out + off) = v;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (n + e < N) ((int8_t *)out)[off + e] = (int8_t)(v >> (8 * e));
-                    }
-                }
-            }
+            if (m < M && n < N) bmm_store4<KIND>(out, bt * M * N + m * N + n, s, n, N, alpha, vec4);
         }
         __syncthreads();   // red is rewritten by the next tile of a grid-stride loop
     }
@@ -356,15 +348,14 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
 // An error of o is common to a row's numerators and its sum and cancels.  With K <= 128 the A tile is loaded once and stays in LDS; the first K step of
 // the next tile is in flight during a tile's epilogue.  CAUSAL: tiles no row of the block can see are skipped in both passes (their B rows are never
 // read) and their outputs zero-filled; only tiles cut by the diagonal or by N take the masked epilogue.
-constexpr int SM_T = 128;
 constexpr float SM_LOG2E = 1.44269502162933349609375f, SM_MAGIC = 12582912.0f;   // 1.5 * 2^23: the low mantissa bits of (x + SM_MAGIC) are rne(x)
 
 template <bool CAUSAL, bool FAST>
 __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, int8_t *__restrict__ out, int64_t M, int64_t N,
                                                       int64_t K, int64_t tiles_m, int64_t total, float alpha, bool vec)
 {
-    __shared__ __attribute__((aligned(16))) char lds[3 * SM_T * BMM_TK];   // [A tile | B tile | output image 128 x 128 B, between the passes the rows' partials]
-    char *const xs = lds, *const ws = lds + SM_T * BMM_TK, *const st = lds + 2 * SM_T * BMM_TK;
+    __shared__ __attribute__((aligned(16))) char lds[3 * BMM_TM * BMM_TK];   // [A tile | B tile | output image 128 x 128 B, between the passes the rows' partials]
+    char *const xs = lds, *const ws = lds + BMM_TM * BMM_TK, *const st = lds + 2 * BMM_TM * BMM_TK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int t16 = lane & 15, q16 = lane >> 4;
     const int64_t nsteps = (K + BMM_TK - 1) / BMM_TK, shift = N - M;
@@ -373,15 +364,15 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
     const int ref0 = neg ? INT32_MAX : INT32_MIN;
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
-        const int64_t bt = id / tiles_m, m0 = (id - bt * tiles_m) * SM_T;
+        const int64_t bt = id / tiles_m, m0 = (id - bt * tiles_m) * BMM_TM;
         const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
-        const int64_t obase = bt * M * N, mlast = (m0 + SM_T < M ? m0 + SM_T : M) - 1;
+        const int64_t obase = bt * M * N, mlast = (m0 + BMM_TM < M ? m0 + BMM_TM : M) - 1;
         auto visible = [&](int64_t m) -> int64_t {   // keys 0 .. visible(m) - 1 are seen by query m
             if (!CAUSAL) return N;
             const int64_t v = m + shift + 1;
             return v < 0 ? 0 : (v > N ? N : v);
         };
-        const int64_t n_end = visible(mlast), nt = (n_end + SM_T - 1) / SM_T, nseq = 2 * nt, nfull = visible(m0);
+        const int64_t n_end = visible(mlast), nt = (n_end + BMM_TN - 1) / BMM_TN, nseq = 2 * nt, nfull = visible(m0);
         int ref[4];
         float l[4], o[4], inv[4];
 #pragma unroll
@@ -417,7 +408,7 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
         if (FAST && nseq > 0 && nsteps > 0) load(0, 0, true);
         for (int64_t u = 0; u < nseq; ++u) {
             const bool second = u >= nt;
-            const int64_t n0 = (second ? u - nt : u) * SM_T;
+            const int64_t n0 = (second ? u - nt : u) * BMM_TN;
             v4i acc[4][4];   // [m tile][n tile] of the wave's 64 x 64
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -429,31 +420,16 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
                 const bool put_a = !a_once || u == 0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int cc = tid + 256 * i, row = cc >> 3, ch = cc & 7;
-                    const int off = row * BMM_TK + ((ch ^ ((row >> 1) & 7)) << 4);
+                    const int cc = tid + 256 * i, off = bmm_tile_off(cc >> 3, cc & 7);
                     if (put_a) *(v4i *)(xs + off) = pkin ? px[i] : (v4i){0, 0, 0, 0};
                     *(v4i *)(ws + off) = pkin ? pw[i] : (v4i){0, 0, 0, 0};
                 }
                 __syncthreads();
                 if constexpr (FAST) {
                     if (s + 1 < nsteps) load(n0, (s + 1) * BMM_TK, true);   // in flight during this step's matrix work ...
-                    else if (u + 1 < nseq) load((u + 1 < nt ? u + 1 : u + 1 - nt) * SM_T, 0, !a_once);   // ... and during the tile's epilogue
+                    else if (u + 1 < nseq) load((u + 1 < nt ? u + 1 : u + 1 - nt) * BMM_TN, 0, !a_once);   // ... and during the tile's epilogue
                 }
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const int ch = kk * 4 + q16;
-                    v4i fx[4], fw[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int rx = wm * 64 + i * 16 + t16, rw = wn * 64 + i * 16 + t16;
-                        fx[i] = *(const v4i *)(xs + rx * BMM_TK + ((ch ^ ((rx >> 1) & 7)) << 4));
-                        fw[i] = *(const v4i *)(ws + rw * BMM_TK + ((ch ^ ((rw >> 1) & 7)) << 4));
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = MmaI8x16::mma(fw[j], fx[i], acc[i][j]);   // lane: row t16 of m tile i, columns 4 q16 .. + 3 of n tile j
-                }
+                bmm_mma_step<false>(xs, ws, wm * 64 + t16, wn * 64 + t16, q16, acc);
             }
 
             // lane-relative number of visible columns of row i in this tile: element (j, e) is visible iff 16 j + e < lim(i)
@@ -513,12 +489,12 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
                             q[e] = __float_as_uint(__builtin_fmaf(ex, inv[i], SM_MAGIC));   // low byte: rne(127 p), 0 .. 127
                         }
                         const uint32_t pk = __builtin_amdgcn_perm(q[1], q[0], 0x0c0c0400u) | __builtin_amdgcn_perm(q[3], q[2], 0x04000c0cu);
-                        *(uint32_t *)(st + ir * SM_T + (((wn * 4 + j) ^ (ir & 7)) << 4) + 4 * q16) = pk;
+                        *(uint32_t *)(st + bmm_stage_off<BMM_TN>(ir, wn * 4 + j) + 4 * q16) = pk;
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            const bool masked = nfull - n0 < SM_T;   // the block's first row (the shortest) does not see the whole tile
+            const bool masked = nfull - n0 < BMM_TN;   // the block's first row (the shortest) does not see the whole tile
             if (!second) {
                 if (masked) pass1(std::true_type{});
                 else pass1(std::false_type{});
@@ -556,14 +532,14 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int idx = tid + 256 * i, ir = idx >> 3, ch = idx & 7;
-                    const v4i v = *(const v4i *)(st + ir * SM_T + ((ch ^ (ir & 7)) << 4));
+                    const v4i v = *(const v4i *)(st + bmm_stage_off<BMM_TN>(ir, ch));
                     const int64_t m = m0 + ir, n = n0 + ch * 16;
                     if (m < M && n < N) bmm_store_chunk<1>(out, obase + m * N + n, v, N - n, vec);
                 }
             }
         }
         // columns behind the last visible tile: zeros
-        const int64_t z0 = nt * SM_T;
+        const int64_t z0 = nt * BMM_TN;
         if (CAUSAL && z0 < N) {
             const int64_t zc = (N - z0 + 15) / 16, rows = mlast - m0 + 1;
             for (int64_t idx = tid; idx < rows * zc; idx += 256) {
@@ -579,38 +555,21 @@ static inline bool bmm_narrow(int64_t M) { return M <= 16; }
 
 static inline int64_t bmm_grid(int64_t total) { return total < (int64_t(1) << 30) ? total : (int64_t(1) << 30); }
 
-template <int KIND>
+template <int KIND, bool KN>   // KN: b is [batch, K, N]
 static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
 {
-    constexpr int EB = BmmOut<KIND>::kBytes;
-    const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
+    constexpr int EB = BmmOut<KIND>::kBytes, NARROW_TN = KN ? BMM_KN_TN : 16 * BMM_NT;
+    const bool fast = (K % 16 == 0) && (!KN || N % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
     if (bmm_narrow(M)) {
-        const int64_t tiles_n = (N + 16 * BMM_NT - 1) / (16 * BMM_NT), total = batch * tiles_n;
+        const int64_t tiles_n = (N + NARROW_TN - 1) / NARROW_TN, total = batch * tiles_n;
         const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
-        hipLaunchKernelGGL((bmm_i8_m16<KIND>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, alpha, fast, vec4);
+        const auto kernel = KN ? bmm_i8_m16kn<KIND> : bmm_i8_m16<KIND>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, alpha, fast, vec4);
     } else {
         const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
         const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
-        hipLaunchKernelGGL((bmm_i8_t128<KIND>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, alpha, fast,
+        hipLaunchKernelGGL((bmm_i8_t128<KIND, KN>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, alpha, fast,
                            vec);
-    }
-    return asq_after_launch(s, "asq_bmm_i8");
-}
-
-template <int KIND>   // b is [batch, K, N]
-static int launch_bmm_kn(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
-{
-    constexpr int EB = BmmOut<KIND>::kBytes;
-    const bool fast = (K % 16 == 0) && (N % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
-    if (bmm_narrow(M)) {
-        const int64_t tiles_n = (N + BMM_KN_TN - 1) / BMM_KN_TN, total = batch * tiles_n;
-        const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
-        hipLaunchKernelGGL((bmm_i8_m16kn<KIND>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, alpha, fast, vec4);
-    } else {
-        const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
-        const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
-        hipLaunchKernelGGL((bmm_i8_t128<KIND, true>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, alpha,
-                           fast, vec);
     }
     return asq_after_launch(s, "asq_bmm_i8");
 }
@@ -618,18 +577,24 @@ static int launch_bmm_kn(const int8_t *a, const int8_t *b, void *out, int64_t ba
 static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
 {
     const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0), vec = (N % 16 == 0) && (((uintptr_t)out & 15) == 0);
-    const int64_t tiles_m = (M + SM_T - 1) / SM_T, total = batch * tiles_m;
-    const dim3 grid((unsigned)bmm_grid(total)), block(256);
-    if (causal && fast) hipLaunchKernelGGL((bmm_i8_sm128<true, true>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
-    else if (causal) hipLaunchKernelGGL((bmm_i8_sm128<true, false>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
-    else if (fast) hipLaunchKernelGGL((bmm_i8_sm128<false, true>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
-    else hipLaunchKernelGGL((bmm_i8_sm128<false, false>), grid, block, 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
+    const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, total = batch * tiles_m;
+    const auto kernel = causal ? (fast ? bmm_i8_sm128<true, true> : bmm_i8_sm128<true, false>) : (fast ? bmm_i8_sm128<false, true> : bmm_i8_sm128<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
     return asq_after_launch(s, "asq_bmm_i8");
 }
 
-static inline bool bmm_softmax_kind(int k) { return k == (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX) || k == (ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL); }
-
-static inline bool bmm_kn_kind(int k) { return k >= (ASQ_BMM_B_KN | ASQ_BMM_S32) && k <= (ASQ_BMM_B_KN | ASQ_BMM_S8); }
+// out_kind = a base kind in the low two bits plus flags.  Valid: 0, 1, 2; ASQ_BMM_B_KN | {0, 1, 2} (128 .. 130); ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]
+// (18, 50).  Every other value, negative ones included, is not.
+struct BmmKind {
+    int base;
+    bool kn, softmax, causal, valid;
+};
+static inline BmmKind bmm_decode(int out_kind)
+{
+    const int base = out_kind & 3, flags = out_kind & ~3;
+    const bool kn = flags == ASQ_BMM_B_KN, softmax = flags == ASQ_BMM_SOFTMAX || flags == (ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL);
+    return {base, kn, softmax, softmax && (flags & ASQ_BMM_CAUSAL) != 0, softmax ? base == ASQ_BMM_S8 : (kn || flags == 0) && base <= ASQ_BMM_S8};
+}
 
 static inline bool bmm_mul(int64_t x, int64_t y, int64_t &r) { return !__builtin_mul_overflow(x, y, &r); }
 
@@ -639,35 +604,33 @@ using namespace asq;
 
 extern "C" const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind)
 {
-    if (batch <= 0 || M <= 0 || N <= 0 || K < 0) return "none";
-    if (bmm_softmax_kind(out_kind)) return "sm128";
-    if (bmm_kn_kind(out_kind)) return bmm_narrow(M) ? "m16kn" : "t128kn";
-    if (out_kind < ASQ_BMM_S32 || out_kind > ASQ_BMM_S8) return "none";
+    const BmmKind kind = bmm_decode(out_kind);
+    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || !kind.valid) return "none";
+    if (kind.softmax) return "sm128";
+    if (kind.kn) return bmm_narrow(M) ? "m16kn" : "t128kn";
     return bmm_narrow(M) ? "m16" : "t128";
 }
 
 extern "C" int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream)
 {
     const AsqRange range_("asq_bmm_i8");
+    const BmmKind kind = bmm_decode(out_kind);
     int64_t mn = 0, bmn = 0, mk = 0, bmk = 0, nk = 0, bnk = 0, bytes = 0;
     ASQ_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, ASQ_ERR_DIM, "asq_bmm_i8: bad dims batch=%lld M=%lld N=%lld K=%lld", (long long)batch,
                 (long long)M, (long long)N, (long long)K);
     ASQ_REQUIRE(bmm_mul(M, N, mn) && bmm_mul(batch, mn, bmn) && bmm_mul(bmn, 4, bytes) && bmm_mul(M, K, mk) && bmm_mul(batch, mk, bmk) && bmm_mul(N, K, nk) &&
                     bmm_mul(batch, nk, bnk),
                 ASQ_ERR_DIM, "asq_bmm_i8: size overflows 64 bits (batch=%lld M=%lld N=%lld K=%lld)", (long long)batch, (long long)M, (long long)N, (long long)K);
-    ASQ_REQUIRE(out_kind == ASQ_BMM_S32 || out_kind == ASQ_BMM_F32 || out_kind == ASQ_BMM_S8 || bmm_softmax_kind(out_kind) || bmm_kn_kind(out_kind), ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
+    ASQ_REQUIRE(kind.valid, ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
     if (bmn == 0) return ASQ_OK;
     ASQ_REQUIRE(out != nullptr, ASQ_ERR_NULL, "asq_bmm_i8: NULL out");
     ASQ_REQUIRE(K == 0 || (a != nullptr && b != nullptr), ASQ_ERR_NULL, "asq_bmm_i8: NULL a / b");
-    ASQ_REQUIRE((out_kind & ~ASQ_BMM_B_KN) == ASQ_BMM_S8 || bmm_softmax_kind(out_kind) || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
+    ASQ_REQUIRE(kind.base == ASQ_BMM_S8 || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
     hipStream_t s = (hipStream_t)stream;
-    if (bmm_softmax_kind(out_kind)) return launch_bmm_softmax(a, b, (int8_t *)out, batch, M, N, K, alpha, (out_kind & ASQ_BMM_CAUSAL) != 0, s);
-    switch (out_kind) {
-    case ASQ_BMM_B_KN | ASQ_BMM_S32: return launch_bmm_kn<ASQ_BMM_S32>(a, b, out, batch, M, N, K, alpha, s);
-    case ASQ_BMM_B_KN | ASQ_BMM_F32: return launch_bmm_kn<ASQ_BMM_F32>(a, b, out, batch, M, N, K, alpha, s);
-    case ASQ_BMM_B_KN | ASQ_BMM_S8: return launch_bmm_kn<ASQ_BMM_S8>(a, b, out, batch, M, N, K, alpha, s);
-    case ASQ_BMM_S32: return launch_bmm<ASQ_BMM_S32>(a, b, out, batch, M, N, K, alpha, s);
-    case ASQ_BMM_F32: return launch_bmm<ASQ_BMM_F32>(a, b, out, batch, M, N, K, alpha, s);
-    default: return launch_bmm<ASQ_BMM_S8>(a, b, out, batch, M, N, K, alpha, s);
+    if (kind.softmax) return launch_bmm_softmax(a, b, (int8_t *)out, batch, M, N, K, alpha, kind.causal, s);
+    switch (kind.base) {
+    case ASQ_BMM_S32: return kind.kn ? launch_bmm<ASQ_BMM_S32, true>(a, b, out, batch, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S32, false>(a, b, out, batch, M, N, K, alpha, s);
+    case ASQ_BMM_F32: return kind.kn ? launch_bmm<ASQ_BMM_F32, true>(a, b, out, batch, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_F32, false>(a, b, out, batch, M, N, K, alpha, s);
+    default: return kind.kn ? launch_bmm<ASQ_BMM_S8, true>(a, b, out, batch, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S8, false>(a, b, out, batch, M, N, K, alpha, s);
     }
 }

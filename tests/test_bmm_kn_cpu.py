@@ -68,6 +68,20 @@ def test_kn_argument_errors_without_gpu(base):
         assert f(1, 3, 5, kind, *empty, 1.0, None) == 0
 
 
+def test_every_out_kind_code_is_decoded_alike_by_the_probe_and_the_entry():
+    """codes -1 .. 511 (every combination of the base bits, the three flags and the bits between and above them): the probe names a kernel exactly when
+    the entry accepts the code -- on an empty problem, which returns before any launch -- and the accepted codes are the eight of include/asq_hip.h"""
+    from autosmoothquant_amd import _lib
+    h = _lib.lib()
+    accepted = set()
+    for kind in range(-1, 512):
+        named = h.asq_bmm_kernel_name(2, 5, 5, 5, kind) != b"none"
+        assert h.asq_bmm_i8(None, None, None, kind, 0, 3, 4, 5, 1.0, None) == (0 if named else -3), kind     # ASQ_OK / ASQ_ERR_DTYPE
+        if named:
+            accepted.add(kind)
+    assert accepted == {0, 1, 2, 18, 50, 128, 129, 130}
+
+
 def test_kn_forward_on_cpu_tensors_raises():
     from autosmoothquant_amd import ops
     from autosmoothquant_amd.layers.functional.bmm import bmm_i8_kn_o8, bmm_i8_kn_o32

@@ -7,6 +7,7 @@ import torch
 
 from autosmoothquant_amd import _lib as L
 from autosmoothquant_amd import ops
+from bmm_ref import assert_bits_equal, ref_out
 from oracle import w8a8 as O
 
 pytestmark = pytest.mark.gpu
@@ -25,21 +26,6 @@ def ref_acc(a, b):
     return out
 
 
-def ref_out(acc, kind, alpha):
-    if kind == torch.int32:
-        return acc
-    y = np.float32(alpha) * acc.astype(np.float32)   # one fp32 product, int -> float rounded to nearest even
-    if kind == torch.float32:
-        return y.astype(np.float32)
-    return np.clip(np.rint(y), -128, 127).astype(np.int8)
-
-
-def bits(x):
-    """bit patterns (f32 outputs compared as integers: -0.0 != 0.0, NaN == NaN)"""
-    x = np.ascontiguousarray(x)
-    return x.view(np.int32) if x.dtype == np.float32 else x
-
-
 def check(a_np, b_np, alpha, kinds=KINDS, a_t=None, b_t=None):
     a_t = torch.from_numpy(a_np).to(DEV) if a_t is None else a_t
     b_t = torch.from_numpy(b_np).to(DEV) if b_t is None else b_t
@@ -48,12 +34,7 @@ def check(a_np, b_np, alpha, kinds=KINDS, a_t=None, b_t=None):
         got = ops.bmm_i8(a_t, b_t, kind, alpha)
         torch.cuda.synchronize()
         assert got.dtype == kind and tuple(got.shape) == (a_np.shape[0], a_np.shape[1], b_np.shape[1])
-        want = ref_out(acc, kind, alpha)
-        g = got.cpu().numpy()
-        if not np.array_equal(bits(g), bits(want)):
-            bad = np.argwhere(bits(g) != bits(want))
-            raise AssertionError(f"{kind} alpha={alpha} shape a{a_np.shape} b{b_np.shape}: {len(bad)} mismatches, first at {bad[0]}: "
-                                 f"got {g[tuple(bad[0])]} want {want[tuple(bad[0])]}")
+        assert_bits_equal(got.cpu().numpy(), ref_out(acc, kind, alpha), f"{kind} alpha={alpha} shape a{a_np.shape} b{b_np.shape}")
     return acc
 
 

@@ -10,6 +10,7 @@ import torch
 
 from autosmoothquant_amd import _lib as L
 from autosmoothquant_amd import ops
+from bmm_ref import assert_bits_equal, bits, medians_us, ref_out, tbits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,24 +26,6 @@ def ref_acc(a, b):
     return np.einsum("bmk,bkn->bmn", a.astype(np.int64), b.astype(np.int64)).astype(np.int32)
 
 
-def ref_out(acc, kind, alpha):
-    if kind == torch.int32:
-        return acc
-    y = np.float32(alpha) * acc.astype(np.float32)   # one fp32 product, int -> float rounded to nearest even
-    if kind == torch.float32:
-        return y.astype(np.float32)
-    return np.clip(np.rint(y), -128, 127).astype(np.int8)
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(np.int32) if x.dtype == np.float32 else x
-
-
-def tbits(t):
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
 def check(a_np, b_np, alpha, kinds=KINDS, a_t=None, b_t=None):
     """b_np is [B, K, N].  Returns the exact accumulator."""
     a_t = dev(a_np) if a_t is None else a_t
@@ -55,12 +38,7 @@ def check(a_np, b_np, alpha, kinds=KINDS, a_t=None, b_t=None):
         assert got.dtype == kind and tuple(got.shape) == (a_np.shape[0], a_np.shape[1], b_np.shape[2]) and got.is_contiguous()
         nk = ops.bmm_i8(a_t, b_nk, kind, alpha)
         assert torch.equal(tbits(got), tbits(nk)), f"{kind} alpha={alpha} a{a_np.shape} b{b_np.shape}: differs from bmm_i8 on the transposed copy"
-        want = ref_out(acc, kind, alpha)
-        g = got.cpu().numpy()
-        if not np.array_equal(bits(g), bits(want)):
-            bad = np.argwhere(bits(g) != bits(want))
-            raise AssertionError(f"{kind} alpha={alpha} a{a_np.shape} b{b_np.shape}: {len(bad)} mismatches, first at {bad[0]}: "
-                                 f"got {g[tuple(bad[0])]} want {want[tuple(bad[0])]}")
+        assert_bits_equal(got.cpu().numpy(), ref_out(acc, kind, alpha), f"{kind} alpha={alpha} a{a_np.shape} b{b_np.shape}")
     return acc
 
 
@@ -293,24 +271,6 @@ def test_graph_capture_replays_attention_forward_kn():
     assert o_out.abs().max() > 20
 
 
-def _medians_us(fns, nrot, reps=20, warm=5):
-    """per function the median HIP-event time of one call, the functions alternating call by call (the same clocks and neighbours for all of them)"""
-    for i in range(warm):
-        for fn in fns:
-            fn(i % nrot)
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for i in range(reps):
-        for j, fn in enumerate(fns):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            fn((i + warm) % nrot)
-            e.record()
-            e.synchronize()
-            times[j].append(s.elapsed_time(e) * 1e3)
-    return [float(np.median(t)) for t in times]
-
-
 def test_prefill_pv_is_faster_than_the_copy_and_the_nk_call():
     """Prefill P.V, 32 heads x 2048 x 128 over 2048 keys, int8 out: one bmm_i8_kn call against the path it replaces in the same run,
     v.transpose(1, 2).contiguous() followed by bmm_i8 -- the same product plus one more pass over V and one more launch, so no margin is added.
@@ -323,8 +283,8 @@ def test_prefill_pv_is_faster_than_the_copy_and_the_nk_call():
     alpha = 1.0 / (127 * 8)
     assert sum(p.numel() + v.numel() for p, v in zip(P, V)) > 256 << 20
     assert torch.equal(ops.bmm_i8_kn(P[0], V[0], torch.int8, alpha), ops.bmm_i8(P[0], V[0].transpose(1, 2).contiguous(), torch.int8, alpha))
-    t_kn, t_old = _medians_us((lambda i: ops.bmm_i8_kn(P[i], V[i], torch.int8, alpha),
-                               lambda i: ops.bmm_i8(P[i], V[i].transpose(1, 2).contiguous(), torch.int8, alpha)), nrot)
+    t_kn, t_old = medians_us((lambda i: ops.bmm_i8_kn(P[i], V[i], torch.int8, alpha),
+                              lambda i: ops.bmm_i8(P[i], V[i].transpose(1, 2).contiguous(), torch.int8, alpha)), nrot)
     print(f"prefill P.V: bmm_i8_kn {t_kn:.1f} us, transpose copy + bmm_i8 {t_old:.1f} us")
     del P, V
     torch.cuda.empty_cache()

@@ -12,6 +12,7 @@ import torch
 import softmax_q8_ref as R
 from autosmoothquant_amd import _lib as L
 from autosmoothquant_amd import ops
+from bmm_ref import medians_us, ref_out
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -195,8 +196,7 @@ def test_unaligned_and_odd_operands():
 
 def ref_pv(p, vt, alpha):
     """the integer restatement of tests/test_hip_bmm.py: sat(rint(fp32(alpha) * fp32(acc)))"""
-    acc = R.acc_exact(p, vt)
-    return np.clip(np.rint(np.float32(alpha) * acc.astype(np.float32)), -128, 127).astype(np.int8)
+    return ref_out(R.acc_exact(p, vt), torch.int8, alpha)
 
 
 @pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
@@ -279,24 +279,6 @@ def test_graph_capture_replays_attention_forward():
     assert o_out.abs().max() > 20
 
 
-def _medians_us(fns, nrot, reps=20, warm=5):
-    """per function the median HIP-event time of one call, the functions alternating call by call (the same clocks and neighbours for all of them)"""
-    for i in range(warm):
-        for fn in fns:
-            fn(i % nrot)
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for i in range(reps):
-        for j, fn in enumerate(fns):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            fn((i + warm) % nrot)
-            e.record()
-            e.synchronize()
-            times[j].append(s.elapsed_time(e) * 1e3)
-    return [float(np.median(t)) for t in times]
-
-
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
 def test_prefill_is_faster_than_the_f32_scores_alone(causal):
     """32 heads x 2048 x 2048, K = 128: the fused call must beat ops.bmm_i8(..., torch.float32) alone in the same run (that call writes four times
@@ -307,7 +289,7 @@ def test_prefill_is_faster_than_the_f32_scores_alone(causal):
     A = [torch.randint(-128, 128, (B, M, K), generator=g, dtype=torch.int8).to(DEV) for _ in range(nrot)]
     Bm = [torch.randint(-128, 128, (B, N, K), generator=g, dtype=torch.int8).to(DEV) for _ in range(nrot)]
     alpha = 4.0 / (5461 * np.sqrt(K))
-    t_f32, t_fused = _medians_us((lambda i: ops.bmm_i8(A[i], Bm[i], torch.float32, alpha), lambda i: ops.bmm_i8_softmax_q8(A[i], Bm[i], alpha, causal)), nrot)
+    t_f32, t_fused = medians_us((lambda i: ops.bmm_i8(A[i], Bm[i], torch.float32, alpha), lambda i: ops.bmm_i8_softmax_q8(A[i], Bm[i], alpha, causal)), nrot)
     print(f"prefill causal={causal}: fused {t_fused:.1f} us, f32 scores alone {t_f32:.1f} us")
     del A, Bm
     torch.cuda.empty_cache()
