@@ -14,6 +14,14 @@ ASQ_FP8_PER_TOKEN, ASQ_FP8_PER_TENSOR, ASQ_FP8_STATIC = 0, 1, 2
 ASQ_BMM_S32, ASQ_BMM_F32, ASQ_BMM_S8 = 0, 1, 2   # asq_bmm_i8 out_kind: int32 acc, alpha * float(acc), sat_i8(rne(alpha * float(acc)))
 ASQ_BMM_SOFTMAX, ASQ_BMM_CAUSAL = 0x10, 0x20    # out_kind flags: ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL] = int8(rne(127 * row softmax(alpha * acc)))
 ASQ_BMM_B_KN = 0x80   # out_kind flag on ASQ_BMM_S32 / _F32 / _S8: b is [batch, K, N] (row-major, N contiguous)
+
+
+
+def ASQ_BMM_B_GROUP(r):
+    """out_kind flag on any asq_bmm_i8 kind, r = 1 .. 256 (1 is the plain code): b holds batch / r entries and entry i of a / out uses b[i // r]"""
+    return (r - 1) << 16
+
+
 # asq_linear_i8_bias kind: the reference's linear_a8_w8_b32_o32 / _b32_o32_with_scaling / _bfp32_ofp32 / _b8_o8 and linear_relu_a8_w8_b8_o8
 ASQ_LIN_B32_O32, ASQ_LIN_B32_O32_SCALED, ASQ_LIN_BF32_OF32, ASQ_LIN_B8_O8, ASQ_LIN_RELU_B8_O8 = 0, 1, 2, 3, 4
 

@@ -23,9 +23,12 @@
 // alignment); the KN kinds also want N % 16 == 0 for the unguarded loads of b (its row pitch).  The kernels take ONE such flag, so a KN call with
 // N % 16 != 0 reads a byte-wise too although only b needs it: correct, slower on such shapes (the plain kernels' signature is kept as it was).
 // Every offset is 64-bit.  No workspace, no split-K across workgroups.
-// What the kernels share is stated once: bmm_tile_off (the swizzled operand image of t128 / sm128), bmm_mma_step (a K step's fragment reads and 16 MFMAs),
-// bmm_stage_off (the output images), bmm_store4 (the finish of m16 / m16kn); on the host bmm_decode (out_kind) and launch_bmm<KIND, KN>.  The tile puts of
-// t128 and sm128 and the K loops of m16 and m16kn stay apart: shared, they would branch on their caller in every line.
+// ASQ_BMM_B_GROUP(r) on any kind: b holds batch / r entries and entry i reads b[i / r] (grouped-query attention: K / V shared by r query heads, never
+// expanded).  The same five kernels, the same grid: the r entries of a group are neighbours in the batch-major order, so they meet on one XCD's L2.
+// What the kernels share is stated once: bmm_b_entry (a batch entry's b), bmm_tile_off (the swizzled operand image of t128 / sm128), bmm_mma_step (a K
+// step's fragment reads and 16 MFMAs), bmm_stage_off (the output images), bmm_store4 (the finish of m16 / m16kn); on the host bmm_decode (out_kind) and
+// launch_bmm<KIND, KN>, which picks the GROUPED instantiations when the group size is above 1.  The tile puts of t128 and sm128 and the K loops of m16
+// and m16kn stay apart: shared, they would branch on their caller in every line.
 #include "asq_gemm_kernels.h"
 
 namespace asq {
@@ -122,6 +125,15 @@ constexpr int BMM_TM = 128, BMM_TN = 128, BMM_TK = 128;
 // chunk ^ ((row >> 1) & 7): conflict-free fragment reads (the image of gemm_i8_p4x16).  The KN image of B passes chunk ^ (row >> 4).
 __device__ __forceinline__ int bmm_tile_off(int row, int chunk) { return row * BMM_TK + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
+// ASQ_BMM_B_GROUP: `group` consecutive batch entries share one b of nk = N * K elements (grouped-query attention: entry i = batch * Hq + h reads KV entry
+// i / group, the r heads of a group being neighbours in the batch-major grid).  Every kernel form finds its b here.  GROUPED is a template flag of the
+// kernels and not a test of group == 1: without it an ungrouped call compiles to what it was before the flag existed (its `group` argument is not read),
+// where one more live scalar moved the register allocation of m16kn and of the int8 t128 and cost them 2 - 3 %.
+template <bool GROUPED> __device__ __forceinline__ const int8_t *bmm_b_entry(const int8_t *b, int64_t bt, int64_t group, int64_t nk)
+{
+    return b + (GROUPED ? bt / group : bt) * nk;
+}
+
 // The output images (t128's staging image, sm128's int8 image): rows of RB bytes, 16-B chunk c of image row ir is stored at c ^ (ir & (RB / 16 - 1)).
 template <int RB> __device__ __forceinline__ int bmm_stage_off(int ir, int c) { return ir * RB + ((c ^ (ir & (RB / 16 - 1))) << 4); }
 
@@ -150,9 +162,9 @@ template <bool KN> __device__ __forceinline__ void bmm_mma_step(const char *xs, 
 // load covers 8 rows of 128 contiguous bytes.  Its B image is [n row][16-B chunks of k] with chunk index ^= ((row >> 1) & 7) ^ (row >> 4): the second term is constant
 // over the 16 rows of a fragment read (the reads stay conflict-free) and spreads the dword writes of a 32-lane half -- 8 nc x 4 (kg & 3), one kg >> 2 -- over all 32 banks.
 // The transpose's registers do not fit the int8 kind's 3 blocks per CU without spilling: KN runs 2 blocks per CU for every kind.
-template <int KIND, bool KN = false>
+template <int KIND, bool KN = false, bool GROUPED = false>
 __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8_t128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
-                                                   int64_t K, int64_t tiles_m, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec)
+                                                   int64_t K, int64_t tiles_m, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec)
 {
     constexpr int EB = BmmOut<KIND>::kBytes, RB = BMM_TN * EB, NC = RB / 16;   // staging image: 64 rows of RB bytes = NC 16-B chunks
     static_assert(64 * RB <= 2 * BMM_TM * BMM_TK, "the staging image reuses the operand tiles");
@@ -165,7 +177,7 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / per_batch, r = id - bt * per_batch;
         const int64_t m0 = (r / tiles_n) * BMM_TM, n0 = (r % tiles_n) * BMM_TN;
-        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
+        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, N * K);
 
         // K step = [128 rows][128 B] of each operand; thread tid moves chunks tid + 256 i (row = chunk >> 3, 16-B column = chunk & 7) into bmm_tile_off's image.
         v4i px[4], pw[4];
@@ -240,9 +252,9 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
 
 constexpr int BMM_NT = 2;   // 16-column MFMA tiles per bmm_i8_m16 block
 
-template <int KIND>
+template <int KIND, bool GROUPED = false>
 __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
-                                                  int64_t K, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec4)
+                                                  int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4)
 {
     __shared__ v4i red[4][BMM_NT][64];   // each wave's partial sums, lane-linear
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -251,7 +263,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / tiles_n, n0 = (id - bt * tiles_n) * (16 * BMM_NT);
-        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
+        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, N * K);
         v4i acc[BMM_NT];
 #pragma unroll
         for (int j = 0; j < BMM_NT; ++j) acc[j] = (v4i){0, 0, 0, 0};
@@ -294,9 +306,9 @@ __device__ __forceinline__ uint32_t load4_kn(const int8_t *base, int64_t N, int6
     return w;
 }
 
-template <int KIND>
+template <int KIND, bool GROUPED = false>
 __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
-                                                    int64_t K, int64_t tiles_n, int64_t total, float alpha, bool fast, bool vec4)
+                                                    int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4)
 {
     __shared__ v4i red[4][4][64];   // each wave's partial sums: [wave][accumulator register][lane], the 4 ints are 4 consecutive columns
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -305,7 +317,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / tiles_n, n0 = (id - bt * tiles_n) * BMM_KN_TN;
-        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * K * N;
+        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, K * N);
         v4i acc[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[e] = (v4i){0, 0, 0, 0};
@@ -350,9 +362,9 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
 // read) and their outputs zero-filled; only tiles cut by the diagonal or by N take the masked epilogue.
 constexpr float SM_LOG2E = 1.44269502162933349609375f, SM_MAGIC = 12582912.0f;   // 1.5 * 2^23: the low mantissa bits of (x + SM_MAGIC) are rne(x)
 
-template <bool CAUSAL, bool FAST>
+template <bool CAUSAL, bool FAST, bool GROUPED = false>
 __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, int8_t *__restrict__ out, int64_t M, int64_t N,
-                                                      int64_t K, int64_t tiles_m, int64_t total, float alpha, bool vec)
+                                                      int64_t K, int64_t tiles_m, int64_t total, int64_t group, float alpha, bool vec)
 {
     __shared__ __attribute__((aligned(16))) char lds[3 * BMM_TM * BMM_TK];   // [A tile | B tile | output image 128 x 128 B, between the passes the rows' partials]
     char *const xs = lds, *const ws = lds + BMM_TM * BMM_TK, *const st = lds + 2 * BMM_TM * BMM_TK;
@@ -365,7 +377,7 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / tiles_m, m0 = (id - bt * tiles_m) * BMM_TM;
-        const int8_t *const ab = a + bt * M * K, *const bb = b + bt * N * K;
+        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, N * K);
         const int64_t obase = bt * M * N, mlast = (m0 + BMM_TM < M ? m0 + BMM_TM : M) - 1;
         auto visible = [&](int64_t m) -> int64_t {   // keys 0 .. visible(m) - 1 are seen by query m
             if (!CAUSAL) return N;
@@ -555,45 +567,56 @@ static inline bool bmm_narrow(int64_t M) { return M <= 16; }
 
 static inline int64_t bmm_grid(int64_t total) { return total < (int64_t(1) << 30) ? total : (int64_t(1) << 30); }
 
-template <int KIND, bool KN>   // KN: b is [batch, K, N]
-static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+template <int KIND, bool KN, bool GROUPED>   // KN: b is [batch, K, N]; GROUPED: group > 1 batch entries per b (bmm_b_entry)
+static int launch_bmm_as(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
 {
     constexpr int EB = BmmOut<KIND>::kBytes, NARROW_TN = KN ? BMM_KN_TN : 16 * BMM_NT;
     const bool fast = (K % 16 == 0) && (!KN || N % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
     if (bmm_narrow(M)) {
         const int64_t tiles_n = (N + NARROW_TN - 1) / NARROW_TN, total = batch * tiles_n;
         const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
-        const auto kernel = KN ? bmm_i8_m16kn<KIND> : bmm_i8_m16<KIND>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, alpha, fast, vec4);
+        const auto kernel = KN ? bmm_i8_m16kn<KIND, GROUPED> : bmm_i8_m16<KIND, GROUPED>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, group, alpha, fast, vec4);
     } else {
         const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
         const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
-        hipLaunchKernelGGL((bmm_i8_t128<KIND, KN>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, alpha, fast,
-                           vec);
+        hipLaunchKernelGGL((bmm_i8_t128<KIND, KN, GROUPED>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, group,
+                           alpha, fast, vec);
     }
     return asq_after_launch(s, "asq_bmm_i8");
 }
+template <int KIND, bool KN> static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    return group > 1 ? launch_bmm_as<KIND, KN, true>(a, b, out, batch, group, M, N, K, alpha, s) : launch_bmm_as<KIND, KN, false>(a, b, out, batch, group, M, N, K, alpha, s);
+}
 
-static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
+template <bool GROUPED>
+static int launch_bmm_softmax_as(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
 {
     const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0), vec = (N % 16 == 0) && (((uintptr_t)out & 15) == 0);
     const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, total = batch * tiles_m;
-    const auto kernel = causal ? (fast ? bmm_i8_sm128<true, true> : bmm_i8_sm128<true, false>) : (fast ? bmm_i8_sm128<false, true> : bmm_i8_sm128<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, total, alpha, vec);
+    const auto kernel = causal ? (fast ? bmm_i8_sm128<true, true, GROUPED> : bmm_i8_sm128<true, false, GROUPED>)
+                               : (fast ? bmm_i8_sm128<false, true, GROUPED> : bmm_i8_sm128<false, false, GROUPED>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, total, group, alpha, vec);
     return asq_after_launch(s, "asq_bmm_i8");
+}
+static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
+{
+    return group > 1 ? launch_bmm_softmax_as<true>(a, b, out, batch, group, M, N, K, alpha, causal, s) : launch_bmm_softmax_as<false>(a, b, out, batch, group, M, N, K, alpha, causal, s);
 }
 
 // out_kind = a base kind in the low two bits plus flags.  Valid: 0, 1, 2; ASQ_BMM_B_KN | {0, 1, 2} (128 .. 130); ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]
-// (18, 50).  Every other value, negative ones included, is not.
+// (18, 50); each of the eight with ASQ_BMM_B_GROUP(r), r - 1 in bits 16 .. 23.  Every other value, negative ones included, is not.
 struct BmmKind {
-    int base;
+    int base, group;
     bool kn, softmax, causal, valid;
 };
 static inline BmmKind bmm_decode(int out_kind)
 {
-    const int base = out_kind & 3, flags = out_kind & ~3;
+    const int group_bits = out_kind & ASQ_BMM_B_GROUP(256), base = out_kind & 3, flags = out_kind & ~(3 | group_bits);
     const bool kn = flags == ASQ_BMM_B_KN, softmax = flags == ASQ_BMM_SOFTMAX || flags == (ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL);
-    return {base, kn, softmax, softmax && (flags & ASQ_BMM_CAUSAL) != 0, softmax ? base == ASQ_BMM_S8 : (kn || flags == 0) && base <= ASQ_BMM_S8};
+    return {base, (group_bits >> 16) + 1, kn, softmax, softmax && (flags & ASQ_BMM_CAUSAL) != 0,
+            softmax ? base == ASQ_BMM_S8 : (kn || flags == 0) && base <= ASQ_BMM_S8};
 }
 
 static inline bool bmm_mul(int64_t x, int64_t y, int64_t &r) { return !__builtin_mul_overflow(x, y, &r); }
@@ -605,7 +628,7 @@ using namespace asq;
 extern "C" const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind)
 {
     const BmmKind kind = bmm_decode(out_kind);
-    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || !kind.valid) return "none";
+    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || !kind.valid || batch % kind.group != 0) return "none";
     if (kind.softmax) return "sm128";
     if (kind.kn) return bmm_narrow(M) ? "m16kn" : "t128kn";
     return bmm_narrow(M) ? "m16" : "t128";
@@ -622,15 +645,17 @@ extern "C" int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_k
                     bmm_mul(batch, nk, bnk),
                 ASQ_ERR_DIM, "asq_bmm_i8: size overflows 64 bits (batch=%lld M=%lld N=%lld K=%lld)", (long long)batch, (long long)M, (long long)N, (long long)K);
     ASQ_REQUIRE(kind.valid, ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
+    ASQ_REQUIRE(batch % kind.group == 0, ASQ_ERR_DIM, "asq_bmm_i8: batch=%lld is no multiple of the b group size %d", (long long)batch, kind.group);
     if (bmn == 0) return ASQ_OK;
     ASQ_REQUIRE(out != nullptr, ASQ_ERR_NULL, "asq_bmm_i8: NULL out");
     ASQ_REQUIRE(K == 0 || (a != nullptr && b != nullptr), ASQ_ERR_NULL, "asq_bmm_i8: NULL a / b");
     ASQ_REQUIRE(kind.base == ASQ_BMM_S8 || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
     hipStream_t s = (hipStream_t)stream;
-    if (kind.softmax) return launch_bmm_softmax(a, b, (int8_t *)out, batch, M, N, K, alpha, kind.causal, s);
+    const int64_t g = kind.group;
+    if (kind.softmax) return launch_bmm_softmax(a, b, (int8_t *)out, batch, g, M, N, K, alpha, kind.causal, s);
     switch (kind.base) {
-    case ASQ_BMM_S32: return kind.kn ? launch_bmm<ASQ_BMM_S32, true>(a, b, out, batch, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S32, false>(a, b, out, batch, M, N, K, alpha, s);
-    case ASQ_BMM_F32: return kind.kn ? launch_bmm<ASQ_BMM_F32, true>(a, b, out, batch, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_F32, false>(a, b, out, batch, M, N, K, alpha, s);
-    default: return kind.kn ? launch_bmm<ASQ_BMM_S8, true>(a, b, out, batch, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S8, false>(a, b, out, batch, M, N, K, alpha, s);
+    case ASQ_BMM_S32: return kind.kn ? launch_bmm<ASQ_BMM_S32, true>(a, b, out, batch, g, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S32, false>(a, b, out, batch, g, M, N, K, alpha, s);
+    case ASQ_BMM_F32: return kind.kn ? launch_bmm<ASQ_BMM_F32, true>(a, b, out, batch, g, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_F32, false>(a, b, out, batch, g, M, N, K, alpha, s);
+    default: return kind.kn ? launch_bmm<ASQ_BMM_S8, true>(a, b, out, batch, g, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S8, false>(a, b, out, batch, g, M, N, K, alpha, s);
     }
 }

@@ -3,6 +3,9 @@
     P = rne(127 * softmax(q_scale * k_scale * sm_scale * (q . k^T)))     BMM_S8T_S8N_SOFTMAX_S8T: int8, 0 .. 127, the scores stay on chip
     O = sat_i8(rne(v_scale / (127 * out_scale) * (P . v)))               pv_bmm's alpha on ops.bmm_i8_kn: v is read as it is stored, [batch, Sk, d]
 
+Grouped-query attention (q [..., Hq, Sq, d] over k, v [..., Hkv, Sk, d], Hq = r * Hkv) takes the same two launches and never expands k or v: the r heads of a
+group become rows of one product, or share b through ASQ_BMM_B_GROUP (forward, _forward_gqa).
+
 The reference stops at the two matmul modules and leaves the softmax between them to the caller (fp32 scores, eager softmax, a cast);
 here the first product carries it as its epilogue.  The state dict is the two scalar buffers ``qk_bmm.a`` and ``pv_bmm.a`` (host-pinned,
 following the module dtype, as in layers/nn/bmm.py)."""
@@ -33,12 +36,33 @@ class Int8Attention(torch.nn.Module):
     def forward(self, q, k, v):
         """q int8 [..., Sq, d], k and v int8 [..., Sk, d] with equal leading dims (flattened to the batch) -> int8 [..., Sq, d].
         Causal masking is bottom-right aligned (query m sees keys n <= m + Sk - Sq), so a decode step with a KV cache sees every key.
-        P . V reads v where it is (ASQ_BMM_B_KN): no transposed copy; only a non-contiguous v is made contiguous first."""
-        if q.dim() < 2 or k.shape != v.shape or q.shape[:-2] != k.shape[:-2] or q.shape[-1] != k.shape[-1]:
+        P . V reads v where it is (ASQ_BMM_B_KN): no transposed copy; only a non-contiguous v is made contiguous first.
+        Grouped-query attention: q [..., Hq, Sq, d] over k and v [..., Hkv, Sk, d] with equal dims before the heads and Hq = r * Hkv; query head h
+        uses KV head h // r.  K and V are never expanded: see _forward_gqa."""
+        if q.dim() < 2 or k.shape != v.shape or q.shape[-1] != k.shape[-1]:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
         lead, sq, d, sk = q.shape[:-2], q.shape[-2], q.shape[-1], k.shape[-2]
-        p = self.qk_bmm(q.reshape(-1, sq, d), k.reshape(-1, sk, d))
+        gqa = lead != k.shape[:-2]
+        if gqa and (q.dim() < 3 or k.dim() != q.dim() or q.shape[:-3] != k.shape[:-3] or k.shape[-3] == 0 or q.shape[-3] % k.shape[-3] != 0):
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
         v3 = v.reshape(-1, sk, d)
         if not v3.is_contiguous():
             v3 = v3.contiguous()
+        if gqa:
+            return self._forward_gqa(q, k.reshape(-1, sk, d), v3, q.shape[-3] // k.shape[-3]).view(*lead, sq, d)
+        p = self.qk_bmm(q.reshape(-1, sq, d), k.reshape(-1, sk, d))
         return ops.bmm_i8_kn(p, v3, torch.int8, self.pv_bmm._alpha()).view(*lead, sq, d)
+
+    def _forward_gqa(self, q, k3, v3, r):
+        """r > 1 query heads per KV head; k3, v3 [B * Hkv, Sk, d] -> [B * Hkv, r * Sq, d], which is [B * Hq, Sq, d].
+        fold (not causal, or Sq == 1): the rows of a product are independent, so the r heads of a group are the r * Sq rows of ONE ungrouped product per KV
+        head -- K and V are read once per KV head, and a decode step fills r of the narrow kernels' 16 rows.  A causal module with Sq == 1 sees every key
+        (bottom-right alignment); the flag is dropped for the call, since with M = r rows it would hide keys.
+        grouped (causal, Sq > 1): the mask depends on a row's position in its own head, so the heads stay batch entries and share b (b_group = r)."""
+        sq, d = q.shape[-2], q.shape[-1]
+        qk_alpha, pv_alpha = self.qk_bmm._alpha(), self.pv_bmm._alpha()
+        if not self.causal or sq == 1:
+            p = ops.bmm_i8_softmax_q8(q.reshape(-1, r * sq, d), k3, qk_alpha, False)
+            return ops.bmm_i8_kn(p, v3, torch.int8, pv_alpha)
+        p = ops.bmm_i8_softmax_q8(q.reshape(-1, sq, d), k3, qk_alpha, True, b_group=r)
+        return ops.bmm_i8_kn(p, v3, torch.int8, pv_alpha, b_group=r)

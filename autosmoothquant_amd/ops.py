@@ -941,15 +941,21 @@ _BMM_KIND = {torch.int32: L.ASQ_BMM_S32, torch.float32: L.ASQ_BMM_F32, torch.int
 _BMM_DTYPE = {code: dt for dt, code in _BMM_KIND.items()}
 
 
-def _bmm(a, b, alpha, out_kind, flags=0):
+def _bmm(a, b, alpha, out_kind, flags=0, b_group=1):
     """The checks, the allocation and the asq_bmm_i8 call of the three ops below: out_kind is a dtype or a plain ASQ_BMM_S32 / _F32 / _S8 code, flags the
-    ASQ_BMM_* flags of the call.  With ASQ_BMM_B_KN among them b is [B, K, N] and the flag may be set on out_kind as well."""
+    ASQ_BMM_* flags of the call.  With ASQ_BMM_B_KN among them b is [B, K, N] and the flag may be set on out_kind as well.  b_group = r (1 .. 256): b has
+    B / r entries and entry i of a uses b[i // r] (ASQ_BMM_B_GROUP)."""
     kn = bool(flags & L.ASQ_BMM_B_KN)
     _dev(a, "a"), _dev(b, "b")
     if a.dtype != torch.int8 or b.dtype != torch.int8:
         raise RuntimeError(f"expected int8 a and b, got {a.dtype} and {b.dtype}")
-    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[1 if kn else 2]:
-        raise ValueError(f"shape mismatch: a {tuple(a.shape)} must be [B, M, K] and b {tuple(b.shape)} {'[B, K, N]' if kn else '[B, N, K]'}")
+    if not (isinstance(b_group, int) and 1 <= b_group <= 256):
+        raise ValueError(f"b_group must be an int in 1 .. 256, got {b_group!r} (a {tuple(a.shape)}, b {tuple(b.shape)})")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] * b_group or a.shape[2] != b.shape[1 if kn else 2]:
+        raise ValueError(f"shape mismatch: a {tuple(a.shape)} must be [B, M, K] and b {tuple(b.shape)} {'[B, K, N]' if kn else '[B, N, K]'}"
+                         + (f" with B / {b_group} entries (b_group)" if b_group != 1 else ""))
+    if b_group != 1:
+        flags |= L.ASQ_BMM_B_GROUP(b_group)
     kind = _BMM_KIND.get(out_kind, out_kind) if isinstance(out_kind, torch.dtype) else out_kind
     if kn and isinstance(kind, int):
         kind &= ~L.ASQ_BMM_B_KN   # 128 .. 130 name the same three kinds
@@ -964,25 +970,27 @@ def _bmm(a, b, alpha, out_kind, flags=0):
     return out
 
 
-def bmm_i8(a, b, out_kind, alpha=1.0):
+def bmm_i8(a, b, out_kind, alpha=1.0, b_group=1):
     """Batched int8 A . B^T (reference bmm_s8t_s8n_{s32t,f32t,s8t}, csrc/kernels/bmm.cu:10-211): a int8 [B, M, K], b int8 [B, N, K] ->
     a new [B, M, N] tensor on the current stream.  out_kind: torch.int32 / L.ASQ_BMM_S32 (the exact accumulator; alpha ignored),
-    torch.float32 / L.ASQ_BMM_F32 (alpha * float(acc)), torch.int8 / L.ASQ_BMM_S8 (sat_i8(rne(alpha * float(acc)))); alpha reaches the kernel as fp32."""
-    return _bmm(a, b, alpha, out_kind)
+    torch.float32 / L.ASQ_BMM_F32 (alpha * float(acc)), torch.int8 / L.ASQ_BMM_S8 (sat_i8(rne(alpha * float(acc)))); alpha reaches the kernel as fp32.
+    b_group = r > 1 (ASQ_BMM_B_GROUP, here and in the two ops below): b has B / r entries and a[i] meets b[i // r] -- the r query heads of a grouped-query
+    model on their shared K or V -- bit-identical to the call on b.repeat_interleave(r, 0) without the copy."""
+    return _bmm(a, b, alpha, out_kind, b_group=b_group)
 
 
-def bmm_i8_kn(a, b, out_kind, alpha=1.0):
+def bmm_i8_kn(a, b, out_kind, alpha=1.0, b_group=1):
     """Batched int8 A . B with b row-major (asq_bmm_i8 with ASQ_BMM_B_KN): a int8 [B, M, K], b int8 [B, K, N] -> a new [B, M, N] tensor on the current
     stream, bit-identical to bmm_i8(a, b.transpose(1, 2).contiguous(), out_kind, alpha) without the copy.  out_kind: as bmm_i8 (a dtype or a plain
     ASQ_BMM_S32 / _F32 / _S8 code); ASQ_BMM_B_KN may be set on a code and is implied."""
-    return _bmm(a, b, alpha, out_kind, L.ASQ_BMM_B_KN)
+    return _bmm(a, b, alpha, out_kind, L.ASQ_BMM_B_KN, b_group)
 
 
-def bmm_i8_softmax_q8(a, b, alpha, causal=False):
+def bmm_i8_softmax_q8(a, b, alpha, causal=False, b_group=1):
     """QK^T with the softmax -> int8 epilogue fused (asq_bmm_i8 with ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]): a int8 [B, M, K], b int8 [B, N, K]
     -> a new int8 [B, M, N] = rne(127 * softmax(alpha * (a . b^T), -1)) on the current stream, values 0 .. 127; the fp32 scores never reach memory.
     causal: key n is visible to query m iff n <= m + (N - M); invisible elements are 0.  alpha reaches the kernel as fp32."""
-    return _bmm(a, b, alpha, L.ASQ_BMM_S8, L.ASQ_BMM_SOFTMAX | (L.ASQ_BMM_CAUSAL if causal else 0))
+    return _bmm(a, b, alpha, L.ASQ_BMM_S8, L.ASQ_BMM_SOFTMAX | (L.ASQ_BMM_CAUSAL if causal else 0), b_group)
 
 
 def bmm_kernel_name(batch, M, N, K, out_kind=L.ASQ_BMM_F32):

@@ -399,7 +399,7 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
 #define ASQ_BMM_F32 1 /* bmm_s8t_s8n_f32t: out float = alpha * float(acc)            */
 #define ASQ_BMM_S8 2  /* bmm_s8t_s8n_s8t : out int8  = sat_i8(rne(alpha*float(acc))) */
 /* out_kind is a base kind in the low bits plus flags.  The valid values are 0, 1, 2, ASQ_BMM_S8 | ASQ_BMM_SOFTMAX (18) and
- * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50), and ASQ_BMM_B_KN | {0, 1, 2} (128, 129, 130); every other value is ASQ_ERR_DTYPE / "none".
+ * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50), and ASQ_BMM_B_KN | {0, 1, 2} (128, 129, 130), each optionally with ASQ_BMM_B_GROUP(r) (bits 16 .. 23, below); every other value is ASQ_ERR_DTYPE / "none".
  *
  * The softmax kinds turn QK^T into the int8 probabilities that P.V consumes (asq_bmm_i8(p, vT, ASQ_BMM_S8) with alpha = v_scale / (127 * out_scale))
  * without the fp32 scores ever reaching memory.  out is int8 [batch, M, N]; per batch i and row m
@@ -425,6 +425,15 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
  * "t128kn" (the 128 x 128 tiles of "t128"; b is transposed on its way into LDS).  No version bump: probe with
  * asq_bmm_kernel_name(batch, M, N, K, 130) != "none"; an older library answers "none". */
 #define ASQ_BMM_B_KN 0x80
+/* ASQ_BMM_B_GROUP(r), r = 1 .. 256, on any of the eight values above (r = 1 is the plain value): r consecutive batch entries share one b.  b then holds
+ * batch / r entries -- [batch / r, N, K], or [batch / r, K, N] with ASQ_BMM_B_KN -- and entry i of a / out uses b[i / r]: grouped-query attention with heads
+ * laid out [B, Hq, S, d], Hq = r * Hkv, where entry i = b * Hq + h reads KV entry b * Hkv + h / r = i / r; K and V are never expanded.  Every output byte
+ * equals the base kind called on b repeated r times along the batch.  Everything else is the base kind's: the epilogues, any M, N, K >= 0, alignment
+ * freedom, K = 0, the empty output, no workspace, determinism, the argument rules and their order.  One more error: batch % r != 0 is ASQ_ERR_DIM, reported
+ * directly after a bad out_kind (so also when M or N is 0); asq_bmm_kernel_name answers "none" for it and otherwise the base kind's name -- these are the
+ * same kernels.  A bit set in 9 .. 15 or in 24 and above stays ASQ_ERR_DTYPE / "none".  No version bump: probe with
+ * asq_bmm_kernel_name(r, M, N, K, kind | ASQ_BMM_B_GROUP(r)) != "none"; an older library answers "none". */
+#define ASQ_BMM_B_GROUP(r) (((r) - 1) << 16)
 int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind,
                int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream);
 const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind);
