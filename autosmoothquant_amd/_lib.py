@@ -17,6 +17,12 @@ ASQ_BMM_B_KN = 0x80   # out_kind flag on ASQ_BMM_S32 / _F32 / _S8: b is [batch, 
 
 
 
+def ASQ_EPI_OUT_SPLIT(n):
+    """epi_order flag of asq_linear_w8a8_off / asq_linear_w8a8, n = 2 .. 4: the N columns are n segments and segment s is its own dense [M, N / n] output at
+    out + s * M * (N / n) elements ([n][M][N / n] instead of [M][N]); (N / n) % 256 == 0, 256 x 256 kernel class only"""
+    return n << 8
+
+
 def ASQ_BMM_B_GROUP(r):
     """out_kind flag on any asq_bmm_i8 kind, r = 1 .. 256 (1 is the plain code): b holds batch / r entries and entry i of a / out uses b[i // r]"""
     return (r - 1) << 16

@@ -34,6 +34,19 @@ static int check_gemm_args(const char *what, const void *x, const void *w, const
     return ASQ_OK;
 }
 
+// epi_order of the dequant entry points: the association order in the low byte, ASQ_EPI_OUT_SPLIT(n) above it (n = 0: one dense output)
+static int parse_epi_order(const char *what, int epi_order, int64_t N, int &order, int &out_split)
+{
+    order = epi_order & 0xFF;
+    out_split = epi_order >> 8;
+    ASQ_REQUIRE(epi_order >= 0 && (order == ASQ_EPI_SCALE_FIRST || order == ASQ_EPI_ACC_FIRST), ASQ_ERR_DTYPE, "%s: bad epi_order %d", what, epi_order);
+    if (out_split == 0) return ASQ_OK;
+    ASQ_REQUIRE(out_split >= 2 && out_split <= 4, ASQ_ERR_DIM, "%s: ASQ_EPI_OUT_SPLIT(n) needs 2 <= n <= 4 (got %d)", what, out_split);
+    ASQ_REQUIRE(N % out_split == 0 && (N / out_split) % 256 == 0, ASQ_ERR_DIM, "%s: ASQ_EPI_OUT_SPLIT(%d) needs N %% n == 0 and (N / n) %% 256 == 0 (N=%lld)", what, out_split,
+                (long long)N);
+    return ASQ_OK;
+}
+
 }  // namespace asq
 
 using namespace asq;
@@ -106,12 +119,15 @@ extern "C" int asq_linear_w8a8(const int8_t *xq, const int8_t *w, void *out, int
     int rc = check_gemm_args("asq_linear_w8a8", xq, w, out, M, N, K);
     if (rc) return rc;
     ASQ_REQUIRE(out_dtype == ASQ_F32 || out_dtype == ASQ_F16 || out_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_linear_w8a8: bad out_dtype %d", out_dtype);
-    ASQ_REQUIRE(epi_order == ASQ_EPI_SCALE_FIRST || epi_order == ASQ_EPI_ACC_FIRST, ASQ_ERR_DTYPE, "asq_linear_w8a8: bad epi_order %d", epi_order);
+    int order, out_split;
+    rc = parse_epi_order("asq_linear_w8a8", epi_order, N, order, out_split);
+    if (rc) return rc;
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(out_dtype)) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8: out misaligned");
     ASQ_REQUIRE((((uintptr_t)s_row | (uintptr_t)s_col | (uintptr_t)bias) & 3) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8: scale/bias misaligned");
     const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
     const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)s_col | (uintptr_t)bias) & 15) == 0);
-    DequantArgs a{xq, w, out, M, N, K, s_scalar, s_row, s_col, bias, epi_order, vec_ok, workspace, workspace_bytes};
+    DequantArgs a{xq, w, out, M, N, K, s_scalar, s_row, s_col, bias, order, vec_ok, workspace, workspace_bytes};
+    a.out_split = out_split;
     hipStream_t s = (hipStream_t)stream;
     switch (out_dtype) {
     case ASQ_F32: return launch_dequant<ASQ_F32>(a, s);
@@ -151,7 +167,9 @@ extern "C" int asq_linear_w8a8_off(const int8_t *xq_off, const int8_t *w_off, vo
     if (rc) return rc;
     if (M == 0 || N == 0) return ASQ_OK;
     ASQ_REQUIRE(out_dtype == ASQ_F16 || out_dtype == ASQ_BF16 || out_dtype == ASQ_F32, ASQ_ERR_DTYPE, "asq_linear_w8a8_off: bad out_dtype %d", out_dtype);
-    ASQ_REQUIRE(epi_order == ASQ_EPI_SCALE_FIRST || epi_order == ASQ_EPI_ACC_FIRST, ASQ_ERR_DTYPE, "asq_linear_w8a8_off: bad epi_order %d", epi_order);
+    int order, out_split;
+    rc = parse_epi_order("asq_linear_w8a8_off", epi_order, N, order, out_split);
+    if (rc) return rc;
     ASQ_REQUIRE(row_off != nullptr && col_off != nullptr, ASQ_ERR_NULL, "asq_linear_w8a8_off: NULL row_off / col_off");
     ASQ_REQUIRE(offsets_shape_ok(xq_off, w_off, M, N, K), ASQ_ERR_DIM,
                 "asq_linear_w8a8_off: needs K %% 128 == 0, 128 <= K <= 65536, N %% 4 == 0 and 16-B aligned operands (M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
@@ -159,8 +177,9 @@ extern "C" int asq_linear_w8a8_off(const int8_t *xq_off, const int8_t *w_off, vo
     ASQ_REQUIRE((((uintptr_t)s_row | (uintptr_t)s_col | (uintptr_t)bias) & 3) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8_off: scale/bias misaligned");
     const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
     const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)s_col | (uintptr_t)bias) & 15) == 0);
-    DequantArgs a{xq_off, w_off, out, M, N, K, s_scalar, s_row, s_col, bias, epi_order, vec_ok, nullptr, 0};
+    DequantArgs a{xq_off, w_off, out, M, N, K, s_scalar, s_row, s_col, bias, order, vec_ok, nullptr, 0};
     a.off = OffsetArgs{row_off, col_off};
+    a.out_split = out_split;
     hipStream_t s = (hipStream_t)stream;
     return out_dtype == ASQ_F16 ? launch_dequant<ASQ_F16>(a, s) : out_dtype == ASQ_BF16 ? launch_dequant<ASQ_BF16>(a, s) : launch_dequant<ASQ_F32>(a, s);
 }
@@ -173,11 +192,14 @@ extern "C" int asq_linear_w8a8_q8(const int8_t *xq, const int8_t *w, int8_t *out
     int rc = check_gemm_args("asq_linear_w8a8_q8", xq, w, out_q, M, N, K);
     if (rc) return rc;
     ASQ_REQUIRE(mid_dtype == ASQ_F32 || mid_dtype == ASQ_F16 || mid_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_linear_w8a8_q8: bad mid_dtype %d", mid_dtype);
-    ASQ_REQUIRE(epi_order == ASQ_EPI_SCALE_FIRST || epi_order == ASQ_EPI_ACC_FIRST, ASQ_ERR_DTYPE, "asq_linear_w8a8_q8: bad epi_order %d", epi_order);
+    int order, out_split;
+    rc = parse_epi_order("asq_linear_w8a8_q8", epi_order, N, order, out_split);
+    if (rc) return rc;
+    ASQ_REQUIRE(out_split == 0, ASQ_ERR_DIM, "asq_linear_w8a8_q8: int8 outputs have no split form (ASQ_EPI_OUT_SPLIT)");
     ASQ_REQUIRE((act == 0 || act == 1) && (qmode == ASQ_ACT_ROUND || qmode == ASQ_ACT_DIV), ASQ_ERR_DTYPE, "asq_linear_w8a8_q8: bad act %d / qmode %d", act, qmode);
     ASQ_REQUIRE((((uintptr_t)s_row | (uintptr_t)s_col | (uintptr_t)bias) & 3) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8_q8: scale/bias misaligned");
     const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out_q & 3) == 0);
-    DequantQArgs a{{xq, w, out_q, M, N, K, s_scalar, s_row, s_col, bias, epi_order, vec_ok, workspace, workspace_bytes}, act, qmode, quant_scale};
+    DequantQArgs a{{xq, w, out_q, M, N, K, s_scalar, s_row, s_col, bias, order, vec_ok, workspace, workspace_bytes}, act, qmode, quant_scale};
     hipStream_t s = (hipStream_t)stream;
     switch (mid_dtype) {
     case ASQ_F32: return launch_dequant_q<ASQ_F32>(a, s);

@@ -25,7 +25,7 @@ static int launch_gate_up(const int8_t *xq, const int8_t *w_gu, int64_t M, int64
         return (int)e;
     }
     const int64_t N = 2 * F, tm = M / 256, tn = N / 256;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)persistent_grid(tm * tn)), dim3(512), P16P_LDS_BYTES, s, xq, w_gu, M, N, K, (int)tm, (int)tn, epi, off);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)persistent_grid(tm * tn)), dim3(512), P16P_LDS_BYTES, s, xq, w_gu, M, N, K, (int)tm, (int)tn, (int)tn, epi, off);
     return asq_after_launch(s, what);
 }
 

@@ -537,6 +537,20 @@ __device__ __forceinline__ void epilogue_wave(const Epi &epi, Get get, MOff moff
     });
 }
 
+// SPLIT OUTPUTS of the 256 x 256 kernels (ASQ_EPI_OUT_SPLIT(n), include/asq_hip.h): the launch's N columns are n segments of Ns = 256 * seg_tiles columns and
+// segment s is its own dense [M, Ns] matrix at out + s * M * Ns elements (n same-input linears in one launch, each with the dense output a launch of its own
+// would write).  The host hands the kernel the segment pitch as the epilogue's row pitch (epi.N = Ns); a 256-wide tile lies in ONE segment, so all that remains
+// is a block-uniform shift of the output base: element (m, n) of the launch is at out + s * M * Ns + m * Ns + (n - s * Ns) = out + s * (M - 1) * Ns + m * Ns + n.
+// The epilogues keep indexing with the launch's (m, n) and the column operands stay [N]-indexed.  n <= 4: three scalar compares, no division; a launch with
+// one dense output passes seg_tiles = tiles_n and gets segment 0.
+__device__ __forceinline__ int out_segment(int tile_n, int seg_tiles) { return (tile_n >= seg_tiles) + (tile_n >= 2 * seg_tiles) + (tile_n >= 3 * seg_tiles); }
+template <class Epi> __device__ __forceinline__ int64_t out_segment_bytes(int seg, int64_t M, int64_t pitch) { return (int64_t)seg * (M - 1) * pitch * Epi::kOutBytes; }
+template <class Epi> __device__ __forceinline__ Epi epi_seg_view(Epi e, int seg, int64_t M)   // (by value, modified unconditionally: see EpiI32::rebased)
+{
+    e.out = (decltype(e.out))uniform_ptr((const int8_t *)e.out + out_segment_bytes<Epi>(seg, M, e.N));   // (pinned to SGPRs: left to the compiler, the fp32 column-scale + bias kernel spills)
+    return e;
+}
+
 struct MmaI8x16 {  // one v_mfma_i32_16x16x64_i8: 16 (A rows) x 16 (B rows) x 64 k-bytes, exact
     static __device__ __forceinline__ v4i mma(const v4i &a, const v4i &b, const v4i &c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
 };
@@ -1238,7 +1252,7 @@ static inline GroupedGrid grouped_grid(int64_t M, int64_t N, int ngroups, bool i
 // One planned launch over the output columns the caller has re-based x / w / epi / N to.  `ws_hdr`: the caller's workspace (header first), `ws`: the scratch behind the header.
 template <class Epi>
 int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const Epi &epi, hipStream_t s, const char *what, void *ws_hdr, void *ws,
-                const OffsetArgs &off)
+                const OffsetArgs &off, int out_split = 0)
 {
     constexpr bool kInt = Epi::Mma::kIsInt;
     constexpr bool kP4 = kInt && Epi::kOutBytes == 2, kP4X = kP4 && !Epi::kHasCol && !Epi::kHasBias, kP16 = kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4);   // (plan_gemm's fallbacks)
@@ -1254,6 +1268,7 @@ int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M
         return ASQ_OK;
     };
     const int64_t tm256 = (M + 255) / 256, tm128 = (M + 127) / 128, tn256 = (N + 255) / 256, tn128 = (N + 127) / 128;
+    const int seg_tiles = (int)(out_split > 1 ? tn256 / out_split : tn256);   // the p16 kernels' tile columns per output segment (out_segment: one dense output = one segment)
     const bool slabs = p.split == SPLIT_SLABS;
     [[maybe_unused]] const EpiI32 slab{(int32_t *)ws, N, true};
     const int *const no_groups = nullptr;
@@ -1279,11 +1294,11 @@ int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M
     case KERN_P16:
         if constexpr (kP16 && Epi::kOutBytes == 2) {
             if (p.persistent) {
-                rc = launch_tiled(gemm_i8_p16p<Epi>, P16P_LDS_BYTES, P16P_LDS_BYTES, persistent_grid(tm256 * tn256), 512, (int)tm256, (int)tn256, epi, off);
+                rc = launch_tiled(gemm_i8_p16p<Epi>, P16P_LDS_BYTES, P16P_LDS_BYTES, persistent_grid(tm256 * tn256), 512, (int)tm256, (int)tn256, seg_tiles, epi, off);
                 break;
             }
         }
-        if constexpr (kP16) rc = launch_tiled(gemm_i8_p16<Epi>, P16_LDS_BYTES, off.row ? P16_LDS_BYTES : P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, epi, off);
+        if constexpr (kP16) rc = launch_tiled(gemm_i8_p16<Epi>, P16_LDS_BYTES, off.row ? P16_LDS_BYTES : P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, seg_tiles, epi, off);
         break;
     case KERN_P8:
         if (slabs) {
@@ -1351,9 +1366,10 @@ int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M
 // `ws` below is the scratch part, `ws_hdr` the whole thing (null when the caller's buffer is too small to hold a header).
 template <class Epi>
 int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, Epi epi, hipStream_t s, const char *what, void *ws_hdr, void *ws,
-                     size_t ws_bytes, const int *goffs = nullptr, int ngroups = 0, OffsetArgs off = OffsetArgs{})
+                     size_t ws_bytes, const int *goffs = nullptr, int ngroups = 0, OffsetArgs off = OffsetArgs{}, int out_split = 0)
 {
     if (M == 0 || N == 0) return ASQ_OK;
+    ASQ_REQUIRE(out_split == 0 || goffs == nullptr, ASQ_ERR_DIM, "%s: a grouped launch has no split outputs", what);
     constexpr bool kInt = Epi::Mma::kIsInt;
     const bool aligned16 = ((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0;
     if constexpr (!IsGroupable<Epi>::value) {
@@ -1385,8 +1401,12 @@ int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int
         ASQ_REQUIRE(kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4) && offsets_shape_ok(x, w, M, N, K), ASQ_ERR_DIM, "%s: offset operands need the 256 x 256 kernel (2- or 4-byte output, K %% 128 == 0, K <= 65536, N %% 4 == 0, aligned operands)", what);
     }
     if constexpr (kInt && Epi::kOutBytes == 2) in.out_rows16 = ((((uintptr_t)epi.out) & 15) == 0) && (epi.N * 2) % 16 == 0 && epi.N * 2 < (int64_t(1) << 24);
+    in.out_split = out_split > 1;
     const GemmPlan plan = plan_gemm(epi_caps<Epi>(), in);
-    int rc = launch_part(plan.part[0], x, w, M, plan.part[0].n, K, epi, s, what, ws_hdr, ws, off);
+    // split outputs (ASQ_EPI_OUT_SPLIT; the entry point has checked n and the segment width): the 256 x 256 kernels only -- the caller's epi.N is the segment pitch
+    ASQ_REQUIRE(!in.out_split || (plan.nparts == 1 && plan.part[0].kern == KERN_P16 && kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4)), ASQ_ERR_DIM,
+                "%s: ASQ_EPI_OUT_SPLIT needs a shape of the 256 x 256 kernel class (M=%lld N=%lld K=%lld runs elsewhere)", what, (long long)M, (long long)N, (long long)K);
+    int rc = launch_part(plan.part[0], x, w, M, plan.part[0].n, K, epi, s, what, ws_hdr, ws, off, out_split);
     if constexpr (HasColView<Epi>::value) {   // a tail peel's column remainder
         const LaunchPlan &r = plan.part[1];
         if (rc == ASQ_OK && plan.nparts == 2) rc = launch_part(r, x, w + r.n0 * K, M, r.n, K, epi.col_view(r.n0), s, what, ws_hdr, ws, off);
@@ -1396,7 +1416,7 @@ int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int
 
 template <class Epi>
 int launch_gemm(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, Epi epi, hipStream_t s, const char *what, void *ws = nullptr,
-                size_t ws_bytes = 0, const int *goffs = nullptr, int ngroups = 0, OffsetArgs off = OffsetArgs{})
+                size_t ws_bytes = 0, const int *goffs = nullptr, int ngroups = 0, OffsetArgs off = OffsetArgs{}, int out_split = 0)
 {
     const bool has = ws != nullptr && ws_bytes >= (size_t)WS_HEADER_BYTES && (((uintptr_t)ws) & 15) == 0;
     if (has && asq_debug_sync()) {   // ASQ_DEBUG_SYNC=1: an uninitialised workspace is an error code here instead of a device trap in the kernels that use its tickets
@@ -1406,7 +1426,7 @@ int launch_gemm(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t 
         ASQ_REQUIRE(e == hipSuccess && magic == WS_MAGIC, ASQ_ERR_WORKSPACE, "%s: workspace header not initialised (asq_workspace_init)", what);
     }
     return launch_gemm_impl(x, w, M, N, K, epi, s, what, has ? ws : nullptr, has ? (char *)ws + WS_HEADER_BYTES : nullptr, has ? ws_bytes - WS_HEADER_BYTES : 0, goffs,
-                            ngroups, off);
+                            ngroups, off, out_split);
 }
 
 // per-dtype instantiation units (asq_gemm_inst_*.hip)
@@ -1424,6 +1444,7 @@ struct DequantArgs {
     const int *goffs = nullptr;
     int ngroups = 0;
     OffsetArgs off;                  // offset operands (asq_linear_w8a8_off)
+    int out_split = 0;               // ASQ_EPI_OUT_SPLIT(n): n dense [M, N / n] outputs, segment-major (0: one [M, N] output)
 };
 template <int DT> int launch_dequant(const DequantArgs &a, hipStream_t s);
 struct DequantQArgs {
@@ -1442,8 +1463,8 @@ template <int DT> static inline int launch_dequant_q_impl(const DequantQArgs &q,
 
 template <int DT, bool R, bool C, bool B> static inline int launch_dequant_one(const DequantArgs &a, hipStream_t s)
 {
-    return launch_gemm(a.xq, a.w, a.M, a.N, a.K, EpiDequant<DT, R, C, B>{a.out, a.N, a.s_row, a.s_col, a.bias, a.s_group, a.s_scalar, a.order, a.vec_ok},
-                       s, "asq_linear_w8a8", a.ws, a.ws_bytes, a.goffs, a.ngroups, a.off);
+    return launch_gemm(a.xq, a.w, a.M, a.N, a.K, EpiDequant<DT, R, C, B>{a.out, a.out_split > 1 ? a.N / a.out_split : a.N, a.s_row, a.s_col, a.bias, a.s_group, a.s_scalar, a.order, a.vec_ok},
+                       s, "asq_linear_w8a8", a.ws, a.ws_bytes, a.goffs, a.ngroups, a.off, a.out_split);
 }
 
 // The 8 epilogue variants of one output dtype are compiled in TWO translation units (with / without per-token row scales: asq_gemm_inst_<dt>.hip,

@@ -30,7 +30,7 @@ namespace asq {
 
 template <class Epi, int ABL = 0>
 __global__ void __launch_bounds__(512, 2) gemm_i8_p16(const int8_t *__restrict__ x, const int8_t *__restrict__ w, int64_t M, int64_t N, int64_t K,
-                                                      int tiles_m, int tiles_n, Epi epi_in, OffsetArgs off)
+                                                      int tiles_m, int tiles_n, int seg_tiles, Epi epi_in, OffsetArgs off)
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -43,7 +43,6 @@ __global__ void __launch_bounds__(512, 2) gemm_i8_p16(const int8_t *__restrict__
     P8_BLK(0);
     constexpr int GM = 4;
     const int id = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    const Epi epi = epi_in.rebased(0, 0, M, N);
     const int per_group = GM * tiles_n;
     const int group = id / per_group, in_group = id - group * per_group;
     const int first_m = group * GM;
@@ -237,10 +236,12 @@ __global__ void __launch_bounds__(512, 2) gemm_i8_p16(const int8_t *__restrict__
     // accumulator tile (in16 = 16-channel tile 0..3, im16 = 16-token tile 0..7) -> rows mw0 + 16*im16, cols nw0 + 16*in16
     auto get = [&](int in16, int im16) -> const v4i & { return acc[im16 >> 2][in16 >> 1][im16 & 3][in16 & 1]; };
     const int64_t mw0 = m0 + wm * 128, nw0 = n0 + wn * 64;
+    // split outputs (ASQ_EPI_OUT_SPLIT, out_segment): the tile's segment moves the output base, nothing else -- block-uniform, formed here, behind the K loop
+    const Epi epi = epi_seg_view(epi_in.rebased(0, 0, M, N), out_segment((int)(n0 >> 8), seg_tiles), M);
     // interior wave tiles leave through the pipelined row epilogues (2-byte: epilogue_wave_rows, 4-byte: epilogue_wave_rows4), edge tiles and unaligned outputs through direct stores
     bool rows_path = ((((uintptr_t)epi.out) & 15) == 0) && ((epi.N * Epi::kOutBytes) % 16 == 0) && mw0 + 128 <= M && nw0 + 64 <= N && epi.N * Epi::kOutBytes < (int64_t(1) << 24);
     P8_BAR();  // (block-uniform) every wave's ring reads are done and every wave's (dead) DMAs have landed: the ring becomes staging space; the staged pairs are visible
-    const bool wt = M * epi.N * Epi::kOutBytes <= (int64_t)ASQ_WT_BYTES && ASQ_WT_BYTES > 0;   // small outputs leave as write-through stores (rows_write_through)
+    const bool wt = M * epi.N * Epi::kOutBytes <= (int64_t)ASQ_WT_BYTES && ASQ_WT_BYTES > 0;   // small outputs leave as write-through stores (rows_write_through; a split launch is judged on one segment: epi.N = Ns)
     auto run = [&](auto getter) {
         if (rows_path) {
             if constexpr (Epi::kOutBytes == 2) epilogue_wave_rows<4, 2, true>(epi, getter, mw0, nw0, lane, lds0 + wave * 16384, wt);

@@ -11,7 +11,9 @@
 //     has no global load, so nothing in it waits behind the prefetched K-tile (gfx950 has ONE vmcnt for loads and stores; loads return in order);
 //   * the epilogue stages in the OTHER LDS stage only (8 KiB per wave: two 4 KiB images used alternately, epilogue_wave_rows<.., IMGS = 2>) and, between its
 //     first conversions and its first store, retires the in-flight operand DMAs with one vmcnt(0) (DRAIN) -- the only point where nothing but they is
-//     outstanding; its stores are write-back (acknowledged by the L2), never write-through;
+//     outstanding; its stores are write-back (acknowledged by the L2) on every tile that has a successor -- a block's LAST tile, which nothing follows,
+//     leaves write-through when the output is small (ASQ_P16P_LAST_WT, rows_write_through: within noise at 4096 x 12288 x 4096 and 16384 x 4096 x 4096,
+//     profiles/out_split_ab.txt section 5);
 //   * the first K-tile of the next tile therefore needs no counted wait in its first two phases (its operands landed before the stores were issued), and the
 //     first counted wait (phase 4) comes ~800 cycles after the last store: it finds them acknowledged.
 // The K loop between the first and the last K-tile is gemm_i8_p16's, instruction for instruction.
@@ -23,6 +25,9 @@
 
 namespace asq {
 
+#ifndef ASQ_P16P_LAST_WT
+#define ASQ_P16P_LAST_WT 1   // a block's LAST tile leaves as write-through stores when the output is small enough (rows_write_through); 0: write-back throughout (A/B)
+#endif
 constexpr int P16P_EAREA = 8192;                                  // one epilogue-operand area: [row pairs 2K | column pairs 2K | s_row 1K | s_col 1K | bias 1K | unused 1K]
 constexpr int P16P_LDS_BYTES = P8_LDS_BYTES + 2 * P16P_EAREA;     // 144 KiB
 
@@ -61,7 +66,7 @@ template <class Epi> struct EpiTileLds {
 
 template <class Epi>
 __global__ void __launch_bounds__(512, 2) gemm_i8_p16p(const int8_t *__restrict__ x, const int8_t *__restrict__ w, int64_t M, int64_t N, int64_t K,
-                                                       int tiles_m, int tiles_n, Epi epi_in, OffsetArgs off)
+                                                       int tiles_m, int tiles_n, int seg_tiles, Epi epi_in, OffsetArgs off)
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int ABL = 0;   // (the P8_* macros' ablation parameter: none here)
@@ -77,6 +82,9 @@ __global__ void __launch_bounds__(512, 2) gemm_i8_p16p(const int8_t *__restrict_
     const bool offs = off.row != nullptr;   // (block-uniform)
     const int nt = (int)(K / 128);          // even, >= 2
     const int klast = (nt - 1) * 128;
+    // (block-uniform.  A split launch is judged on ONE segment here, epi.N = Ns, as in gemm_i8_p16: n <= 4 segments of <= 128 MiB -- the policy of a launch
+    // between 128 and 512 MiB of output differs from the dense launch's; not measured, results are the same either way)
+    const bool wt_last = ASQ_P16P_LAST_WT && rows_write_through(M, epi);
 
     const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)lds;
     const unsigned dma_dst = lds0 + wave * 2048;
@@ -277,13 +285,14 @@ __global__ void __launch_bounds__(512, 2) gemm_i8_p16p(const int8_t *__restrict_
 
         // ---- epilogue: staging in stage 1 only (8 KiB per wave), operands from the LDS area
         const int64_t mw0 = m0 + wm * 128, nw0 = n0 + wn * 64;
-        const EpiTileLds<Epi> el{epi, ea, m0, n0, epi.out, epi.N};
+        // (split outputs: the tile's segment moves its output base by a scalar -- out_segment, asq_gemm_kernels.h; one dense output: segment 0)
+        const EpiTileLds<Epi> el{epi, ea, m0, n0, (char *)epi.out + out_segment_bytes<Epi>(out_segment((int)(n0 >> 8), seg_tiles), M, epi.N), epi.N};
         const unsigned stage = lds0 + P8_STAGE + wave * 8192;
         int le = lane;   // an opaque copy per tile: every lane-derived address of the epilogue is tile-invariant, and hoisted out of the tile loop it would live through the K loop
         asm volatile("" : "+v"(le));
         auto emit = [&](auto getter) {
             if constexpr (IsGateUp<Epi>::value) epilogue_gate_up(el, getter, mw0, nw0, le);   // gate || up GEMM: SiLU(gate) * up, half the output bytes (asq_gemm_gateup.h)
-            else epilogue_wave_rows<4, 2, true, 2, true>(el, getter, mw0, nw0, le, stage, false);
+            else epilogue_wave_rows<4, 2, true, 2, true>(el, getter, mw0, nw0, le, stage, wt_last && !has_next);   // (no tile follows the last one: nothing counts on its stores)
         };
         if (offs) {
             const int t16i = le & 15, q16i = le >> 4;

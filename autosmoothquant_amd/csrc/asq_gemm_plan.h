@@ -271,9 +271,10 @@ struct PlanInput {
     size_t scratch_bytes;    // ... this much 16-byte aligned scratch
     bool offsets = false;    // offset operand images (OffsetArgs)
     bool out_rows16 = false; // 2-byte outputs: out is 16-byte aligned, its row stride a multiple of 16 bytes below 2^24 (the persistent kernel's row stores)
+    bool out_split = false;  // split outputs (ASQ_EPI_OUT_SPLIT): one launch of the 256 x 256 class, never a tail peel (launch_gemm_impl rejects every other plan)
     bool sizing = false;     // workspace query: a 128 x 128 split counts the larger of its two forms, whatever ASQ_SPLITK_FIX / ASQ_MMA select at launch
 };
-inline PlanInput plan_query(int64_t M, int64_t N, int64_t K, bool aligned16 = true) { return PlanInput{M, N, K, aligned16, true, (size_t)-1, false, false, true}; }
+inline PlanInput plan_query(int64_t M, int64_t N, int64_t K, bool aligned16 = true) { return PlanInput{M, N, K, aligned16, true, (size_t)-1, false, false, false, true}; }
 
 enum SplitForm { SPLIT_NONE, SPLIT_SLABS, SPLIT_IN_LAUNCH };
 struct LaunchPlan {
@@ -377,7 +378,7 @@ static inline GemmPlan plan_gemm(const EpiCaps &caps, const PlanInput &in)
     g.cls = in.offsets ? KERN_P16 : pick_kernel(in.aligned16, M, in.N, K);   // (offset operands: gemm_i8_p16 only; the entry points have checked the shape)
     // the peel is planned on the class; its main part (a launch with >= 256 tiles never splits K: no workspace) then goes through the dispatcher like a problem
     // of its own, the remainder has its kernel fixed
-    if (caps.is_int && caps.col_view && !in.offsets && (in.N * caps.out_bytes) % 16 == 0) {
+    if (caps.is_int && caps.col_view && !in.offsets && !in.out_split && (in.N * caps.out_bytes) % 16 == 0) {
         const TailPeel tp = plan_tail_peel(g.cls, M, in.N, K);
         if (tp.n_main > 0) {
             plan_part(g.part[0], pick_kernel(in.aligned16, M, tp.n_main, K), 0, tp.n_main, false);

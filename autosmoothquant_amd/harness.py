@@ -155,8 +155,129 @@ side_streams_enabled = _os.environ.get("ASQ_SIDE_STREAMS", "0") == "1"
 _SIDE = {}
 
 
+# ---- same-input linears of equal width as ONE launch with split outputs (ASQ_EPI_OUT_SPLIT) -------------------------------------
+# q/k/v (gate/up) on one stream are three (two) single-round launches of the 256 x 256 kernel, each paying the whole per-launch fixed cost; as one launch over the
+# stacked weights they are a multi-round launch of the persistent kernel, which hides most of it -- and with split outputs every module still gets the dense
+# [M, N] tensor its own forward returns.  The stacked operand is no third copy of the weights: the modules' offset images LIVE in it (adopt_image_buffers).
+# ASQ_MERGE_LINEARS=0 keeps the per-module launches (A/B); results are bit-identical either way.
+# Not merged (they run one by one as before): plain-operand runs (ASQ_OFFSETS=0, shapes without images), unequal widths (GQA k / v against q), biased beside
+# bias-free modules, per-token and per-tensor consumers in one run, a single module (o_proj), modules whose own launch already has more than one round of tiles.
+merge_linears_enabled = _os.environ.get("ASQ_MERGE_LINEARS", "1") != "0"
+MERGE_MAX = 4           # ASQ_EPI_OUT_SPLIT(n): n = 2 .. 4
+MERGE_MIN_TILES = 256   # one round of 256 x 256 tiles (one per CU): the merged launch must have more, each module's own launch at most that many
+
+
+def _merge_key(m):
+    """what modules of one merged run share, or None for a module that never merges"""
+    from .layers.nn.linear import W8A8BFP32OFP32Linear, W8A8BFP32OFP32LinearWithQuantScale
+    if type(m) not in (W8A8BFP32OFP32Linear, W8A8BFP32OFP32LinearWithQuantScale) or m.out_features % 256 != 0:
+        return None
+    return (m.in_features, m.out_features, m.act_quant, bool(m.use_bias))
+
+
+class _MergedRun:
+    """The stacked operand of one run of modules: w [n * N, K] int8 and col [n * N, 2] int32 whose slices ARE the modules' image buffers, and the [n * N] column
+    scales filled from the modules' host scalars (re-keyed on their values, as W8A8BFP32OFP32QKVLinear._scale_vector)."""
+
+    def __init__(self, mods):
+        self.mods, self.w, self.col, self.scol, self.bias = tuple(mods), None, None, None, None
+
+    def operands(self, M, dtype, capturing):
+        """(w, col) with every module's current image in place, or None (a module without an image; a rebuild needed inside a capture)"""
+        n, N = len(self.mods), self.mods[0].out_features
+        images = [m.offset_image(M, dtype) for m in self.mods]
+        if any(im is None for im in images):
+            return None
+        if self.w is not None and all(im[0].data_ptr() == self.w[i * N].data_ptr() and im[1].data_ptr() == self.col[i * N].data_ptr() for i, im in enumerate(images)):
+            return self.w, self.col
+        if capturing:
+            return None
+        dev = images[0][0].device
+        if self.w is None or self.w.device != dev:
+            self.w = torch.empty((n * N, self.mods[0].in_features), dtype=torch.int8, device=dev)
+            self.col = torch.empty((n * N, 2), dtype=torch.int32, device=dev)
+        for i, m in enumerate(self.mods):   # (a module that moved or got fresh buffers takes its slice again)
+            if m.adopt_image_buffers(self.w[i * N:(i + 1) * N], self.col[i * N:(i + 1) * N]) is None:
+                return None
+        return self.w, self.col
+
+    def biases(self, device, capturing):
+        """the [n * N] fp32 bias of a run of biased modules, or None when one would have to be built inside a capture.  Like the images, the vector is no copy: each
+        module's `bias` buffer BECOMES its slice (same values, same dtype, a view), so in-place writes and load_state_dict land in the stack; a module whose bias
+        is another tensor by now (.to(), an assignment) takes its slice again."""
+        N = self.mods[0].out_features
+        cur = [m._bias_on(device) for m in self.mods]
+        if self.bias is not None and all(b.data_ptr() == self.bias[i * N].data_ptr() for i, b in enumerate(cur)):
+            return self.bias
+        if capturing:
+            return None
+        if self.bias is None or self.bias.device != device:
+            self.bias = torch.empty((len(self.mods) * N,), dtype=torch.float32, device=device)
+        for i, (m, b) in enumerate(zip(self.mods, cur)):
+            if b.data_ptr() != self.bias[i * N].data_ptr():
+                self.bias[i * N:(i + 1) * N].copy_(b)
+                m.bias = self.bias[i * N:(i + 1) * N]
+        return self.bias
+
+    def scales(self, device, capturing):
+        vals = tuple(m._scalar("dequant_scale") for m in self.mods)
+        key = (vals, str(device))
+        if self.scol is None or self.scol[0] != key:
+            if capturing:
+                return None
+            N = self.mods[0].out_features
+            self.scol = (key, torch.cat([torch.full((N,), v, dtype=torch.float32) for v in vals]).to(device))
+        return self.scol[1]
+
+
+def _merged_forward(mods, xi):
+    """the outputs of mods (2 .. MERGE_MAX modules of one _merge_key) on xi as one split-output launch, or None when this call cannot run that way"""
+    per_token = mods[0].act_quant == "per-token"
+    M, N = xi.xq.shape[0], mods[0].out_features
+    own = ((M + 255) // 256) * (N // 256)      # 256 x 256 tiles of one module's own launch
+    # (only single-round launches merge: each pays the whole per-launch fixed cost.  A module with more than one round of tiles already runs on the persistent
+    # kernel -- merged gate / up at 4096 x 11008 measured 0.4 % SLOWER per layer step, profiles/out_split_ab.txt)
+    if (xi.xq.shape[-1] != mods[0].in_features or per_token != (xi.s_row is not None)
+            or own > MERGE_MIN_TILES or own * len(mods) <= MERGE_MIN_TILES):
+        return None
+    run = mods[0].__dict__.get("_merged_run")
+    if run is None or len(run.mods) != len(mods) or any(a is not b for a, b in zip(run.mods, mods)):
+        run = mods[0].__dict__["_merged_run"] = _MergedRun(mods)
+    capturing = torch.cuda.is_current_stream_capturing()
+    ops_ = run.operands(M, xi.out_dtype, capturing)
+    if ops_ is None:
+        return None
+    s_col = run.scales(xi.xq.device, capturing)
+    if s_col is None:
+        return None
+    bias = None
+    if mods[0].use_bias:
+        bias = run.biases(xi.xq.device, capturing)
+        if bias is None:
+            return None
+    from . import ops
+    out = ops.linear_w8a8_off(xi.xq, ops_[0], xi.row_off, ops_[1], xi.out_dtype, 1.0, xi.s_row, s_col, bias, out_split=len(mods))
+    return [out[i].view(*xi.lead, N) for i in range(len(mods))]
+
+
+def _merged_linears(mods, xi):
+    """[m(xi) for m in mods], maximal runs of 2 .. MERGE_MAX consecutive mergeable modules as one launch each"""
+    outs, i = [], 0
+    while i < len(mods):
+        key, j = _merge_key(mods[i]), i + 1
+        while key is not None and j < len(mods) and j - i < MERGE_MAX and _merge_key(mods[j]) == key:
+            j += 1
+        got = _merged_forward(mods[i:j], xi) if j - i >= 2 else None
+        outs.extend(got if got is not None else [m(xi) for m in mods[i:j]])
+        i = j
+    return outs
+
+
 def concurrent_linears(mods, xi):
-    """[m(xi) for m in mods] with modules 2.. running on side streams (fork after `xi` is ready on the current stream, join before returning)."""
+    """[m(xi) for m in mods].  Runs of same-width modules on an offset-image activation go as one split-output launch each (_merged_linears); with
+    ASQ_SIDE_STREAMS=1 modules 2.. run on side streams instead (fork after `xi` is ready on the current stream, join before returning)."""
+    if merge_linears_enabled and not side_streams_enabled and len(mods) >= 2 and getattr(xi, "row_off", None) is not None:
+        return _merged_linears(list(mods), xi)
     t = xi.xq if hasattr(xi, "xq") else xi
     if (not side_streams_enabled or len(mods) < 2 or not isinstance(t, torch.Tensor) or not t.is_cuda
             or t.numel() // t.shape[-1] < SIDE_STREAM_MIN_ROWS):

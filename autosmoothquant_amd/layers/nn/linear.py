@@ -245,6 +245,22 @@ class _W8A8Base(torch.nn.Module):
             return False
         return self._image_buffers(w, self._weight_key(w)) is not None
 
+    def adopt_image_buffers(self, w_off, col_off):
+        """Make (w_off int8 [N,K], col_off int32 [N,2]) this module's image buffers and build the image into them now.  For callers that run several modules
+        as ONE launch over a stacked operand (harness.concurrent_linears): each module gets its slice of the stack as its buffers, and the module's own key and
+        version logic keeps that slice current from then on -- no second copy of the image is kept current.  Buffers the module held before (build_offset_image
+        at load time, an earlier stack) are retired, not freed: graphs captured on them stay valid but see no later weight update.  Returns the image, or None."""
+        w = self._buffers["weight"]
+        if not (self.offsets and w.is_cuda) or w_off.device != w.device or tuple(w_off.shape) != tuple(w.shape):
+            return None
+        hit = self.__dict__.get("_offset_cache")
+        if hit is not None and hit[1][0].data_ptr() != w_off.data_ptr():
+            # the buffers this module held so far stay allocated: a hipGraph captured on them keeps replaying on valid memory (with the image as of now -- they
+            # are no longer refreshed; INTEGRATION.md section 8, "Lifetime of an image")
+            self.__dict__.setdefault("_offset_retired", []).append(hit[1])
+        self.__dict__["_offset_cache"] = (None, (w_off, col_off))   # (no weight has this key: _image_buffers rebuilds, into these buffers)
+        return self._image_buffers(w, self._weight_key(w))
+
     def invalidate_offset_image(self):
         """Mark the cached image stale: the next eager forward that wants it rebuilds it into the same buffers.  (In-place torch operations on a weight with a
         version counter, .to() and replica.broadcast_quantized are detected without this; load_state_dict calls it.)"""

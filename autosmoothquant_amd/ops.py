@@ -410,8 +410,10 @@ def quantize_act_off(x, mode, quant_scale=1.0):
     return xq, s_row, row_off
 
 
-def linear_w8a8_off(xq_off, w_off, row_off, col_off, out_dtype, s_scalar=1.0, s_row=None, s_col=None, bias=None, order="scale_first", out=None):
-    """linear_w8a8 on offset operand images: bit-identical to linear_w8a8 on the plain operands (asq_linear_w8a8_off)."""
+def linear_w8a8_off(xq_off, w_off, row_off, col_off, out_dtype, s_scalar=1.0, s_row=None, s_col=None, bias=None, order="scale_first", out=None, out_split=0):
+    """linear_w8a8 on offset operand images: bit-identical to linear_w8a8 on the plain operands (asq_linear_w8a8_off).
+    out_split = n (2 .. 4, ASQ_EPI_OUT_SPLIT): the N weight rows are n stacked linears of N / n outputs each and the result is [n, M, N / n] -- out[s] is the
+    dense [M, N / n] output of a call on rows s * N / n .. of w_off / col_off / s_col / bias; (N / n) % 256 == 0."""
     _dev(xq_off, "xq"), _dev(w_off, "weight"), _dev(row_off, "row_off"), _dev(col_off, "col_off")
     if xq_off.dtype != torch.int8 or w_off.dtype != torch.int8 or xq_off.dim() != 2 or w_off.dim() != 2 or xq_off.shape[1] != w_off.shape[1]:
         raise ValueError("xq [M,K] and weight [N,K] must be int8 with equal K")
@@ -424,18 +426,21 @@ def linear_w8a8_off(xq_off, w_off, row_off, col_off, out_dtype, s_scalar=1.0, s_
             _dev(t, name)
             if t.dtype != torch.float32 or t.numel() != n:
                 raise ValueError(f"{name} must be float32 with {n} elements")
+    if out_split and (out_split < 2 or N % out_split != 0):
+        raise ValueError(f"out_split={out_split} must be 2 .. 4 and divide N={N}")
+    shape = (out_split, M, N // out_split) if out_split else (M, N)
     if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=xq_off.device)
+        out = torch.empty(shape, dtype=out_dtype, device=xq_off.device)
     else:
         _dev(out, "out")
-        if out.dtype != out_dtype or tuple(out.shape) != (M, N):
+        if out.dtype != out_dtype or tuple(out.shape) != shape:
             raise ValueError("out has wrong dtype/shape")
         _bump_version(out)
     dev = _same_device(xq_off, w_off, out, row_off, col_off, s_row, s_col, bias)
+    flags = (L.ASQ_EPI_SCALE_FIRST if order == "scale_first" else L.ASQ_EPI_ACC_FIRST) | (L.ASQ_EPI_OUT_SPLIT(out_split) if out_split else 0)
     with _on(dev):
         L.check(L.lib().asq_linear_w8a8_off(xq_off.data_ptr(), w_off.data_ptr(), out.data_ptr(), _DT[out_dtype], M, N, K, float(s_scalar),
-                                            _ptr(s_row), _ptr(s_col), _ptr(bias), L.ASQ_EPI_SCALE_FIRST if order == "scale_first" else L.ASQ_EPI_ACC_FIRST,
-                                            row_off.data_ptr(), col_off.data_ptr(), _stream(xq_off)), "asq_linear_w8a8_off")
+                                            _ptr(s_row), _ptr(s_col), _ptr(bias), flags, row_off.data_ptr(), col_off.data_ptr(), _stream(xq_off)), "asq_linear_w8a8_off")
     return out
 
 

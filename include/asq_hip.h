@@ -50,6 +50,13 @@ extern "C" {
 /* association order of the dequant epilogue */
 #define ASQ_EPI_SCALE_FIRST 0 /* (s_col*s_row) * float(acc) + bias   -- nn modules, linear.py:93,104,200-206 */
 #define ASQ_EPI_ACC_FIRST 1   /* (float(acc)*s_col) * s_row  + bias  -- functional/quantization.py:103-120   */
+/* ASQ_EPI_OUT_SPLIT(n), n = 2 .. 4, or-ed onto either order in the epi_order of asq_linear_w8a8_off (and of asq_linear_w8a8 where the call runs on the 256 x 256
+ * kernel class): SPLIT OUTPUTS -- n same-input linears of equal width as ONE launch over their stacked weights, each with the dense output a launch of its own
+ * would write.  The N columns are n segments of Ns = N / n columns; segment s is a dense row-major [M, Ns] matrix at out + s * M * Ns elements (out is
+ * [n][M][Ns] instead of [M][N]); w, col_off, s_col and bias stay [N]-indexed.  Bit-identical to n calls on the operand slices.  Needs N % n == 0 and
+ * Ns % 256 == 0; every other n, an int8 output (asq_linear_w8a8_q8) and a shape that does not run on the 256 x 256 kernels are ASQ_ERR_DIM.  No tail peel, no
+ * workspace use.  Present iff the header defines it: no new entry point, asq_version() unchanged. */
+#define ASQ_EPI_OUT_SPLIT(n) ((n) << 8)
 
 /* status codes */
 #define ASQ_OK 0

@@ -350,7 +350,7 @@ template <class Epi> static void run_gemm_p16(const char *name, const int8_t *x,
     const int tm = (int)((M + 255) / 256), tn = (int)((N + 255) / 256), nb = tm * tn < 4096 ? tm * tn : 4096;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     const int BATCH = 50;
-    auto launch = [&]() { hipLaunchKernelGGL(kfn, dim3(tm * tn), dim3(512), P16_LDS_BYTES, 0, x, w, M, N, K, tm, tn, epi, off); };
+    auto launch = [&]() { hipLaunchKernelGGL(kfn, dim3(tm * tn), dim3(512), P16_LDS_BYTES, 0, x, w, M, N, K, tm, tn, tn, epi, off); };
     for (int i = 0; i < 5; ++i) launch();
     CK(hipDeviceSynchronize());
     smp.start();
