@@ -503,16 +503,10 @@ static int launch_mx_tiled_one(const int8_t *xq, const uint8_t *xs, const int8_t
     const size_t vbytes = DT == ASQ_F32 ? 16 : 8;
     const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)bias) & 15) == 0);
     Epi epi{out, N, nullptr, bias, nullptr, 1.0f, 1.0f, false, vec_ok};  // unit epilogue scales: the block scales are inside the product
-    auto kfn = gemm_i8_p8q<Epi, true>;
-    hipError_t e = ensure_dynamic_lds((const void *)kfn, P8Q_MX_LDS_BYTES);
-    if (e != hipSuccess) {
-        asq_set_error("asq_linear_mxfp8: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
     const int64_t tm = (M + 127) / 128, tn = (N + 127) / 128;
     ASQ_REQUIRE(tm * tn < (1ll << 24), ASQ_ERR_DIM, "asq_linear_mxfp8: too many tiles");
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(tm * tn)), dim3(512), P8Q_MX_LDS_BYTES, s, xq, wq, M, N, K, (int)tm, (int)tn, 1, epi, xs, ws);
-    return asq_after_launch(s, "asq_linear_mxfp8");
+    const int rc = launch_lds("asq_linear_mxfp8", gemm_i8_p8q<Epi, true>, P8Q_MX_LDS_BYTES, P8Q_MX_LDS_BYTES, tm * tn, 512, s, xq, wq, M, N, K, (int)tm, (int)tn, 1, epi, xs, ws);
+    return rc != ASQ_OK ? rc : asq_after_launch(s, "asq_linear_mxfp8");
 }
 static int launch_mx_tiled(int out_dtype, const int8_t *xq, const uint8_t *xs, const int8_t *wq, const uint8_t *ws, void *out, int64_t M, int64_t N, int64_t K,
                            const float *bias, hipStream_t s)

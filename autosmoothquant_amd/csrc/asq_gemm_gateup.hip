@@ -18,15 +18,9 @@ extern "C" int asq_gate_up_supported(int64_t M, int64_t F, int64_t K, int out_dt
 template <class Epi>
 static int launch_gate_up(const int8_t *xq, const int8_t *w_gu, int64_t M, int64_t F, int64_t K, const Epi &epi, OffsetArgs off, hipStream_t s, const char *what)
 {
-    auto kfn = gemm_i8_p16p<Epi>;
-    const hipError_t e = ensure_dynamic_lds((const void *)kfn, P16P_LDS_BYTES);
-    if (e != hipSuccess) {
-        asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-        return (int)e;
-    }
     const int64_t N = 2 * F, tm = M / 256, tn = N / 256;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)persistent_grid(tm * tn)), dim3(512), P16P_LDS_BYTES, s, xq, w_gu, M, N, K, (int)tm, (int)tn, (int)tn, epi, off);
-    return asq_after_launch(s, what);
+    const int rc = launch_lds(what, gemm_i8_p16p<Epi>, P16P_LDS_BYTES, P16P_LDS_BYTES, persistent_grid(tm * tn), 512, s, xq, w_gu, M, N, K, (int)tm, (int)tn, (int)tn, epi, off);
+    return rc != ASQ_OK ? rc : asq_after_launch(s, what);
 }
 
 extern "C" int asq_linear_w8a8_gate_up_q8(const int8_t *xq, const int8_t *w_gu, int8_t *out_q, int act_dtype, int64_t M, int64_t F, int64_t K, float s_gate, float s_up,
@@ -98,19 +92,14 @@ static int launch_grouped_gate_up(const int8_t *xq, const int8_t *w_gu, void *ou
     const bool has_header = ws != nullptr && ws_bytes >= (size_t)WS_HEADER_BYTES;
     const GroupedGrid gg = grouped_grid(M, N, ngroups, true, has_header, has_header ? ws_bytes - WS_HEADER_BYTES : 0);
     ASQ_REQUIRE(gg.tiles < (1ll << 24), ASQ_ERR_DIM, "asq_linear_w8a8_grouped_gate_up: too many tiles");
-    auto kfn = gemm_i8_p8<Epi, 0, true, true>;
     const bool g_offs = off.row != nullptr;
     const int lds = g_offs ? P16_LDS_BYTES : P8_LDS_BYTES;
-    const hipError_t e = ensure_dynamic_lds((const void *)kfn, lds);
-    if (e != hipSuccess) {
-        asq_set_error("asq_linear_w8a8_grouped_gate_up: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
     Epi epi{out, F, nullptr, 1.0f, 1.0f, 1.0f, fast};
     epi.sg_group = s_gate;
     epi.su_group = s_up;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)gg.tiles), dim3(512), lds, s, xq, w_gu, M, N, K, 0, (int)tn, 1, goffs, ngroups, gg.tail_split ? (char *)ws : nullptr, epi, g_offs ? off : OffsetArgs{});
-    return asq_after_launch(s, "asq_linear_w8a8_grouped_gate_up");
+    const int rc = launch_lds("asq_linear_w8a8_grouped_gate_up", gemm_i8_p8<Epi, 0, true, true>, lds, lds, gg.tiles, 512, s, xq, w_gu, M, N, K, 0, (int)tn, 1, goffs, ngroups,
+                              gg.tail_split ? (char *)ws : nullptr, epi, g_offs ? off : OffsetArgs{});
+    return rc != ASQ_OK ? rc : asq_after_launch(s, "asq_linear_w8a8_grouped_gate_up");
 }
 
 extern "C" int asq_linear_w8a8_grouped_gate_up(const int8_t *xq, const int8_t *w_gu, void *out, int out_dtype, const int32_t *group_offsets, int ngroups, int64_t M, int64_t F,
@@ -157,15 +146,10 @@ static int launch_fp8_grouped_gate_up(const int8_t *xq, const int8_t *w_gu, void
     const int64_t N = 2 * F, tn = N / 256;
     const int64_t tiles = grouped_grid(M, N, ngroups, false, false, 0).tiles;
     ASQ_REQUIRE(tiles < (1ll << 24), ASQ_ERR_DIM, "asq_linear_fp8_grouped_gate_up: too many tiles");
-    auto kfn = gemm_i8_p8<Epi, 0, true, false>;
-    const hipError_t e = ensure_dynamic_lds((const void *)kfn, P8_LDS_BYTES);
-    if (e != hipSuccess) {
-        asq_set_error("asq_linear_fp8_grouped_gate_up: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
     const Epi epi{out, F, a_scale, s_gate, s_up, 1.0f, 1.0f, fast};
-    hipLaunchKernelGGL(kfn, dim3((unsigned)tiles), dim3(512), P8_LDS_BYTES, s, xq, w_gu, M, N, K, 0, (int)tn, 1, goffs, ngroups, (char *)nullptr, epi, OffsetArgs{});
-    return asq_after_launch(s, "asq_linear_fp8_grouped_gate_up");
+    const int rc = launch_lds("asq_linear_fp8_grouped_gate_up", gemm_i8_p8<Epi, 0, true, false>, P8_LDS_BYTES, P8_LDS_BYTES, tiles, 512, s, xq, w_gu, M, N, K, 0, (int)tn, 1, goffs, ngroups,
+                              (char *)nullptr, epi, OffsetArgs{});
+    return rc != ASQ_OK ? rc : asq_after_launch(s, "asq_linear_fp8_grouped_gate_up");
 }
 
 extern "C" int asq_linear_fp8_grouped_gate_up(const uint8_t *xq, const uint8_t *w_gu, void *out, int out_dtype, const int32_t *group_offsets, int ngroups, int64_t M, int64_t F,

@@ -22,6 +22,10 @@
 //   2. then all tiles are converted and stored with no memory wait in between
 //      (on gfx9 stores count in vmcnt: a load-wait inside the store loop would serialise the
 //      stores on their write acknowledgements -- measured 2.7x on the whole epilogue).
+//
+// Stated once in this file: the ragged 4-wide store behind the functors' vector stores (store4_bounded), the launch of every kernel with dynamic LDS
+// (launch_lds) and the slab-writer / MFMA-form choice of the 128- and 256-row kernel classes (launch_slab_or_epi).  The wave-tile finish of p8 / p8h /
+// p8q / p8q2 (epilogue_wave_rows | epilogue_wave_staged | direct stores) is still written at each kernel's end: DESIGN.md section 4 says why.
 #pragma once
 #include "asq_common.h"
 #include "asq_gemm_plan.h"
@@ -146,6 +150,15 @@ struct MmaBf8 {  // OCP e5m2 x e5m2 -> fp32
 // ---------------------------------------------------------------------------------
 // epilogue functors
 // ---------------------------------------------------------------------------------
+// The ragged right edge of a row at p: of its 4 columns n .. n + 3, those below Ncols exist and get p[i] = value(i).  The scalar path behind a functor's vector store.
+template <class T, class F> __device__ __forceinline__ void store4_bounded(T *p, int64_t n, int64_t Ncols, F value)
+{
+    if (n < Ncols) p[0] = value(0);
+    if (n + 1 < Ncols) p[1] = value(1);
+    if (n + 2 < Ncols) p[2] = value(2);
+    if (n + 3 < Ncols) p[3] = value(3);
+}
+
 struct EpiI32 {
     using Mma = MmaI8;
     static constexpr bool kHasRow = false, kHasCol = false, kHasBias = false;
@@ -165,14 +178,8 @@ struct EpiI32 {
     __device__ __forceinline__ void store4(int64_t m, int64_t n, const v4i &a, float, const v4f &, const v4f &, int64_t Ncols) const
     {
         int32_t *p = out + m * N + n;
-        if (vec_ok && n + 3 < Ncols) {
-            *(v4i *)p = a;
-        } else {
-            if (n < Ncols) p[0] = a[0];
-            if (n + 1 < Ncols) p[1] = a[1];
-            if (n + 2 < Ncols) p[2] = a[2];
-            if (n + 3 < Ncols) p[3] = a[3];
-        }
+        if (vec_ok && n + 3 < Ncols) *(v4i *)p = a;
+        else store4_bounded(p, n, Ncols, [&](int i) __attribute__((always_inline)) { return a[i]; });
     }
 };
 
@@ -288,22 +295,18 @@ template <int DT, bool HAS_ROW, bool HAS_COL, bool HAS_BIAS> struct EpiDequant {
     __device__ __forceinline__ void store4(int64_t m, int64_t n, const v4i &a, float sr, const v4f &sc, const v4f &b, int64_t Ncols) const
     {
         using E = ElemT<DT>;
-        const float v0 = one(a[0], sc[0], sr, b[0]), v1 = one(a[1], sc[1], sr, b[1]);
-        const float v2 = one(a[2], sc[2], sr, b[2]), v3 = one(a[3], sc[3], sr, b[3]);
+        const float v[4] = {one(a[0], sc[0], sr, b[0]), one(a[1], sc[1], sr, b[1]), one(a[2], sc[2], sr, b[2]), one(a[3], sc[3], sr, b[3])};
         typename E::type *p = (typename E::type *)out + m * N + n;
         if (vec_ok && n + 3 < Ncols) {
             if constexpr (DT == ASQ_F32) {
-                *(v4f *)p = (v4f){v0, v1, v2, v3};
+                *(v4f *)p = (v4f){v[0], v[1], v[2], v[3]};
             } else {
-                const uint32_t lo = (uint32_t)E::store(v0) | ((uint32_t)E::store(v1) << 16);
-                const uint32_t hi = (uint32_t)E::store(v2) | ((uint32_t)E::store(v3) << 16);
+                const uint32_t lo = (uint32_t)E::store(v[0]) | ((uint32_t)E::store(v[1]) << 16);
+                const uint32_t hi = (uint32_t)E::store(v[2]) | ((uint32_t)E::store(v[3]) << 16);
                 *(uint2 *)p = make_uint2(lo, hi);
             }
         } else {
-            if (n < Ncols) p[0] = E::store(v0);
-            if (n + 1 < Ncols) p[1] = E::store(v1);
-            if (n + 2 < Ncols) p[2] = E::store(v2);
-            if (n + 3 < Ncols) p[3] = E::store(v3);
+            store4_bounded(p, n, Ncols, [&](int i) __attribute__((always_inline)) { return E::store(v[i]); });
         }
     }
 };
@@ -419,15 +422,20 @@ template <int DT, bool HAS_BIAS, class MMA_ = MmaFp8> struct EpiFp8 {
     using Mma = MMA_;
     static constexpr bool kHasRow = true, kHasCol = false, kHasBias = HAS_BIAS;
     static constexpr int kOutBytes = (DT == ASQ_F32) ? 4 : 2;
-    __device__ __forceinline__ auto pack(const v4f &a, float sr, const v4f &sc, const v4f &b) const
+    // the 4 finished values, before their conversion to DT
+    __device__ __forceinline__ void finish4(float (&v)[4], const v4f &a, float sr, const v4f &sc, const v4f &b) const
     {
-        using E = ElemT<DT>;
-        float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             v[i] = __fmul_rn(a[i], __fmul_rn(sr, sc[i]));
             if constexpr (HAS_BIAS) v[i] = __fadd_rn(v[i], b[i]);
         }
+    }
+    __device__ __forceinline__ auto pack(const v4f &a, float sr, const v4f &sc, const v4f &b) const
+    {
+        using E = ElemT<DT>;
+        float v[4];
+        finish4(v, a, sr, sc, b);
         if constexpr (DT == ASQ_F32) {
             return __builtin_bit_cast(v4i, (v4f){v[0], v[1], v[2], v[3]});
         } else if constexpr (DT == ASQ_F16) {  // two conversions + the pack per instruction, as EpiDequant::pack
@@ -473,11 +481,7 @@ template <int DT, bool HAS_BIAS, class MMA_ = MmaFp8> struct EpiFp8 {
     {
         using E = ElemT<DT>;
         float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i] = __fmul_rn(a[i], __fmul_rn(sr, sc[i]));
-            if constexpr (HAS_BIAS) v[i] = __fadd_rn(v[i], b[i]);
-        }
+        finish4(v, a, sr, sc, b);
         typename E::type *p = (typename E::type *)out + m * N + n;
         if (vec_ok && n + 3 < Ncols) {
             if constexpr (DT == ASQ_F32) {
@@ -488,10 +492,7 @@ template <int DT, bool HAS_BIAS, class MMA_ = MmaFp8> struct EpiFp8 {
                 *(uint2 *)p = make_uint2(lo, hi);
             }
         } else {
-            if (n < Ncols) p[0] = E::store(v[0]);
-            if (n + 1 < Ncols) p[1] = E::store(v[1]);
-            if (n + 2 < Ncols) p[2] = E::store(v[2]);
-            if (n + 3 < Ncols) p[3] = E::store(v[3]);
+            store4_bounded(p, n, Ncols, [&](int i) __attribute__((always_inline)) { return E::store(v[i]); });
         }
     }
 };
@@ -1143,6 +1144,19 @@ static inline hipError_t ensure_dynamic_lds(const void *kfn, int bytes)
     return e;
 }
 
+// THE LAUNCH of every kernel with dynamic LDS: the attribute once (lds_attr bytes: the most any launch of this kernel asks for), its error reported under the
+// caller's name, then `lds` bytes for this launch.  The caller follows up with asq_after_launch once its launches are out.
+template <class Kfn, class... Args> int launch_lds(const char *what, Kfn kfn, int lds_attr, size_t lds, int64_t grid, int block, hipStream_t s, Args... args)
+{
+    const hipError_t e = ensure_dynamic_lds((const void *)kfn, lds_attr);
+    if (e != hipSuccess) {
+        asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+        return (int)e;
+    }
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)block), lds, s, args...);
+    return ASQ_OK;
+}
+
 // ---------------------------------------------------------------------------------
 // split-K tail: sum S int32 slabs [S][M][N] (exact, order-free) and run the fused epilogue.
 // One thread per 4 consecutive channels of one token; N % 4 == 0 (enforced by the launcher).
@@ -1188,27 +1202,13 @@ template <class Epi, int MT, int NT> int launch_skinny_mt(const int8_t *x, const
     int64_t grid = 256 * per_cu;   // persistent beyond that: blocks walk the items grid-stride
     if (grid > nitems) grid = nitems;
     const size_t lds = (size_t)(wpb * perwave);
-    auto kfn = gemm_i8_skinny<Epi, MT, NT>;
-    hipError_t e = ensure_dynamic_lds((const void *)kfn, (int)lds);
-    if (e != hipSuccess) {
-        asq_set_error("skinny: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)(wpb * 64)), lds, s, x, w, M, N, K, wpb, mblocks, epi);
-    return ASQ_OK;
+    return launch_lds("skinny", gemm_i8_skinny<Epi, MT, NT>, (int)lds, lds, grid, wpb * 64, s, x, w, M, N, K, wpb, mblocks, epi);
 }
 
 template <class Epi, int MT, bool WNT>
 int launch_wstream_mt(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const WsPlan &p, char *ws, const Epi &epi, hipStream_t s)
 {
-    auto kfn = gemm_i8_wstream<Epi, MT, WNT>;
-    hipError_t e = ensure_dynamic_lds((const void *)kfn, WsCfg<MT>::LDS);
-    if (e != hipSuccess) {
-        asq_set_error("wstream: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)p.G), dim3(512), WsCfg<MT>::LDS, s, x, w, M, N, K, p.KU, p.T, p.maxseg, ws, epi);
-    return ASQ_OK;
+    return launch_lds("wstream", gemm_i8_wstream<Epi, MT, WNT>, WsCfg<MT>::LDS, WsCfg<MT>::LDS, p.G, 512, s, x, w, M, N, K, p.KU, p.T, p.maxseg, ws, epi);
 }
 
 // the weight stream as planned: the stream-K kernel over the caller's workspace (p.ws.G > 0; ws_hdr = the workspace, header first) or the first-generation kernel
@@ -1249,6 +1249,20 @@ static inline GroupedGrid grouped_grid(int64_t M, int64_t N, int ngroups, bool i
     return g;
 }
 
+// The 128- and 256-row kernel classes (KERN_P8, KERN_P8H, KERN_P8Q) come in two MFMA forms, and each runs the split-K slab writer or the caller's epilogue:
+// run(epilogue, form) with form = std::true_type for the 16 x 16 x 64 form (plan: p.l16; int8 only, L16_OK says whether the caller's epilogue has one).
+template <bool SLABS_OK, bool L16_OK, class Epi, class Run> int launch_slab_or_epi(const LaunchPlan &p, const EpiI32 &slab, const Epi &epi, Run run)
+{
+    if (p.split == SPLIT_SLABS) {
+        if constexpr (SLABS_OK) return p.l16 ? run(slab, std::true_type{}) : run(slab, std::false_type{});
+        else return ASQ_OK;
+    }
+    if constexpr (L16_OK) {
+        if (p.l16) return run(epi, std::true_type{});
+    }
+    return run(epi, std::false_type{});
+}
+
 // One planned launch over the output columns the caller has re-based x / w / epi / N to.  `ws_hdr`: the caller's workspace (header first), `ws`: the scratch behind the header.
 template <class Epi>
 int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M, int64_t N, int64_t K, const Epi &epi, hipStream_t s, const char *what, void *ws_hdr, void *ws,
@@ -1256,16 +1270,10 @@ int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M
 {
     constexpr bool kInt = Epi::Mma::kIsInt;
     constexpr bool kP4 = kInt && Epi::kOutBytes == 2, kP4X = kP4 && !Epi::kHasCol && !Epi::kHasBias, kP16 = kInt && (Epi::kOutBytes == 2 || Epi::kOutBytes == 4);   // (plan_gemm's fallbacks)
-    // the tiled kernels: one launcher (dynamic-LDS attribute once per kernel, launch) and one split-K tail (exact int32 slabs, then reduce + the caller's epilogue)
+    // the tiled kernels: one launcher and one split-K tail (exact int32 slabs, then reduce + the caller's epilogue)
     auto launch_tiled = [&](auto kfn, int lds_attr, int lds, int64_t grid, int block, auto... args) -> int {
         ASQ_REQUIRE(grid < (1ll << 24), ASQ_ERR_DIM, "%s: too many tiles", what);
-        const hipError_t e = ensure_dynamic_lds((const void *)kfn, lds_attr);
-        if (e != hipSuccess) {
-            asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-            return (int)e;
-        }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)block), lds, s, x, w, M, N, K, args...);
-        return ASQ_OK;
+        return launch_lds(what, kfn, lds_attr, lds, grid, block, s, x, w, M, N, K, args...);
     };
     const int64_t tm256 = (M + 255) / 256, tm128 = (M + 127) / 128, tn256 = (N + 255) / 256, tn128 = (N + 127) / 128;
     const int seg_tiles = (int)(out_split > 1 ? tn256 / out_split : tn256);   // the p16 kernels' tile columns per output segment (out_segment: one dense output = one segment)
@@ -1300,46 +1308,22 @@ int launch_part(const LaunchPlan &p, const int8_t *x, const int8_t *w, int64_t M
         }
         if constexpr (kP16) rc = launch_tiled(gemm_i8_p16<Epi>, P16_LDS_BYTES, off.row ? P16_LDS_BYTES : P8_LDS_BYTES, tm256 * tn256, 512, (int)tm256, (int)tn256, seg_tiles, epi, off);
         break;
-    case KERN_P8:
-        if (slabs) {
-            if constexpr (kInt) rc = p.l16 ? p8(gemm_i8_p8<EpiI32, 0, false, true>, slab) : p8(gemm_i8_p8<EpiI32>, slab);
-        } else {
-            if constexpr (kInt && !kP16) {   // (int8 outputs at p16's sizes)
-                if (p.l16) {
-                    rc = p8(gemm_i8_p8<Epi, 0, false, true>, epi);
-                    break;
-                }
-            }
-            rc = p8(gemm_i8_p8<Epi>, epi);
-        }
+    case KERN_P8:   // (its 16 x 16 x 64 form with the caller's epilogue: int8 outputs at p16's sizes)
+        rc = launch_slab_or_epi<kInt, kInt && !kP16>(p, slab, epi, [&](const auto &e, auto l16) { return p8(gemm_i8_p8<std::decay_t<decltype(e)>, 0, false, decltype(l16)::value>, e); });
         break;
     case KERN_P8H:
-        if (slabs) {
-            if constexpr (kInt) rc = p.l16 ? p8h(gemm_i8_p8h<EpiI32, false, true>, slab) : p8h(gemm_i8_p8h<EpiI32>, slab);
-        } else {
-            if constexpr (kInt) {
-                if (p.l16) {
-                    rc = p8h(gemm_i8_p8h<Epi, false, true>, epi);
-                    break;
-                }
-            }
-            rc = p8h(gemm_i8_p8h<Epi>, epi);
-        }
+        rc = launch_slab_or_epi<kInt, kInt>(p, slab, epi, [&](const auto &e, auto l16) { return p8h(gemm_i8_p8h<std::decay_t<decltype(e)>, false, decltype(l16)::value>, e); });
         break;
     case KERN_P8Q:
         if (p.split == SPLIT_IN_LAUNCH) {
             if constexpr (kP16) rc = p8q2(gemm_i8_p8q2<Epi, true>, epi, (char *)ws_hdr);
-        } else if (slabs) {
-            if constexpr (kInt) rc = p.l16 ? p8q2(gemm_i8_p8q2<EpiI32>, slab, nullptr) : p8q(gemm_i8_p8q<EpiI32>, slab);
-        } else {
-            if constexpr (kInt) {
-                if (p.l16) {
-                    rc = p8q2(gemm_i8_p8q2<Epi>, epi, nullptr);
-                    break;
-                }
-            }
-            rc = p8q(gemm_i8_p8q<Epi>, epi);
+            break;
         }
+        rc = launch_slab_or_epi<kInt, kInt>(p, slab, epi, [&](const auto &e, auto l16) {   // (the 16 x 16 x 64 form is a kernel of its own)
+            using E = std::decay_t<decltype(e)>;
+            if constexpr (decltype(l16)::value) return p8q2(gemm_i8_p8q2<E>, e, nullptr);
+            else return p8q(gemm_i8_p8q<E>, e);
+        });
         break;
     case KERN_SKINNY:
         rc = launch_skinny(p, x, w, M, N, K, epi, s, ws_hdr);
@@ -1387,14 +1371,9 @@ int launch_gemm_impl(const int8_t *x, const int8_t *w, int64_t M, int64_t N, int
         if constexpr (kInt && Epi::kOutBytes == 2) g_offs = off.row != nullptr && !mma32_forced();
         ASQ_REQUIRE(off.row == nullptr || (g_offs && K <= OFFSET_MAX_K && N % 4 == 0), ASQ_ERR_DIM, "%s: offset operands need int8 groups, 2-byte outputs, K <= 65536, N %% 4 == 0", what);
         const int lds = g_offs ? P16_LDS_BYTES : P8_LDS_BYTES;
-        const hipError_t e = ensure_dynamic_lds((const void *)kfn, lds);
-        if (e != hipSuccess) {
-            asq_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-            return (int)e;
-        }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)gg.tiles), dim3(512), lds, s, x, w, M, N, K, 0, (int)((N + 255) / 256), 1, goffs, ngroups, gg.tail_split ? (char *)ws_hdr : nullptr, epi,
-                           g_offs ? off : OffsetArgs{});
-        return asq_after_launch(s, what);
+        const int rc = launch_lds(what, kfn, lds, lds, gg.tiles, 512, s, x, w, M, N, K, 0, (int)((N + 255) / 256), 1, goffs, ngroups, gg.tail_split ? (char *)ws_hdr : nullptr, epi,
+                                  g_offs ? off : OffsetArgs{});
+        return rc != ASQ_OK ? rc : asq_after_launch(s, what);
     }
     PlanInput in{M, N, K, aligned16, ws_hdr != nullptr, ws_bytes, off.row != nullptr};
     if (in.offsets) {   // offset operands: gemm_i8_p16 only (the entry point has checked the shape: asq_offsets_supported)

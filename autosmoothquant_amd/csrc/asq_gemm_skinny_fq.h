@@ -379,17 +379,10 @@ int launch_skinny_fq_nt(const void *x, const int8_t *w, void *out, int64_t M, in
     int64_t grid = 256 * per_cu;   // persistent beyond that: a block walks its channel tiles grid-stride and quantises once
     if (grid > ntiles) grid = ntiles;
     const size_t lds = (size_t)(ximg + wpb * perwave);
-    auto kfn = gemm_i8_skinny_fq<DT, NT, STG>;
-    hipError_t e = ensure_dynamic_lds((const void *)kfn, (int)lds);
-    if (e != hipSuccess) {
-        asq_set_error("skinny_fq: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }
     static const int abl = [] { const char *e = getenv("ASQ_FQ_ABL"); return e ? atoi(e) : 0; }();   // development: 1 = no activation loads, 2 = prologue only (timing only, results invalid)
     const int div_fast = ((quant_scale > 0x1p-60f && quant_scale < 0x1p60f) ? 1 : 0) | (abl << 8);   // (bit 0 as quantize_dt: the exact division without dividing, inside its validity range)
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)(wpb * 64)), lds, s, x, w, (int)M, N, K, wpb, mr, mode, quant_scale, div_fast,
-                       FqEpi<DT>{out, s_col, bias, s_scalar});
-    return ASQ_OK;
+    return launch_lds("skinny_fq", gemm_i8_skinny_fq<DT, NT, STG>, (int)lds, lds, grid, wpb * 64, s, x, w, (int)M, N, K, wpb, mr, mode, quant_scale, div_fast,
+                      FqEpi<DT>{out, s_col, bias, s_scalar});
 }
 
 template <int DT>
