@@ -28,6 +28,15 @@ def ASQ_BMM_B_GROUP(r):
     return (r - 1) << 16
 
 
+# out_kind flags on any asq_bmm_i8 kind, with ASQ_BMM_HEADS(h): the operand is token-major, [B, rows, heads, cols] (_OUT_TOKEN not on the softmax kinds)
+ASQ_BMM_A_TOKEN, ASQ_BMM_B_TOKEN, ASQ_BMM_OUT_TOKEN = 0x200, 0x400, 0x800
+
+
+def ASQ_BMM_HEADS(h):
+    """out_kind field that goes with the ASQ_BMM_*_TOKEN flags, h = 2 .. 128: batch entries (heads of a / out) per sequence; entry i is head i % h of sequence i // h"""
+    return (h - 1) << 24
+
+
 # asq_linear_i8_bias kind: the reference's linear_a8_w8_b32_o32 / _b32_o32_with_scaling / _bfp32_ofp32 / _b8_o8 and linear_relu_a8_w8_b8_o8
 ASQ_LIN_B32_O32, ASQ_LIN_B32_O32_SCALED, ASQ_LIN_BF32_OF32, ASQ_LIN_B8_O8, ASQ_LIN_RELU_B8_O8 = 0, 1, 2, 3, 4
 

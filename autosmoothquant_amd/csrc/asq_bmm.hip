@@ -25,7 +25,9 @@
 // Every offset is 64-bit.  No workspace, no split-K across workgroups.
 // ASQ_BMM_B_GROUP(r) on any kind: b holds batch / r entries and entry i reads b[i / r] (grouped-query attention: K / V shared by r query heads, never
 // expanded).  The same five kernels, the same grid: the r entries of a group are neighbours in the batch-major order, so they meet on one XCD's L2.
-// What the kernels share is stated once: bmm_b_entry (a batch entry's b), bmm_tile_off (the swizzled operand image of t128 / sm128), bmm_mma_step (a K
+// ASQ_BMM_A_TOKEN / _B_TOKEN / _OUT_TOKEN with ASQ_BMM_HEADS(h) on any kind: the flagged operands are [sequences, rows, heads, cols], as q/k/v projections write
+// them and o_proj reads them.  The same five kernels with a head offset and a row pitch per operand (bmm_entry); nothing else moves.
+// What the kernels share is stated once: bmm_b_entry and bmm_entry (a batch entry's operands and pitches), bmm_tile_off (the swizzled operand image of t128 / sm128), bmm_mma_step (a K
 // step's fragment reads and 16 MFMAs), bmm_stage_off (the output images), bmm_store4 (the finish of m16 / m16kn); on the host bmm_decode (out_kind) and
 // launch_bmm<KIND, KN>, which picks the GROUPED instantiations when the group size is above 1.  The tile puts of t128 and sm128 and the K loops of m16
 // and m16kn stay apart: shared, they would branch on their caller in every line.
@@ -134,6 +136,34 @@ template <bool GROUPED> __device__ __forceinline__ const int8_t *bmm_b_entry(con
     return b + (GROUPED ? bt / group : bt) * nk;
 }
 
+// ASQ_BMM_A_TOKEN / _B_TOKEN / _OUT_TOKEN with ASQ_BMM_HEADS(h): batch entry bt is head bt % h of sequence bt / h, and a flagged operand is [sequences, rows, heads,
+// cols] instead of [entries, rows, cols].  A sequence's block has the same size either way (h entries of M * K, h / group of N * K, h of M * N); within it head x
+// starts x * (cols) in and a row is heads * cols long when the operand is token-major, x * rows * cols in with rows of cols when it is dense.  The host states
+// both per operand (bmm_tok); b's head is head / group, which for a dense b is the entry bt / group of bmm_b_entry.  TOKEN is a template flag for GROUPED's
+// reason: the instantiations without it never read `tok`, take their pitches from K and N and are what they were (profiles/bmm_token_resources.txt).  The
+// TOKEN forms take the group at run time (1 when there is none): one more instantiation per form, not two.  They divide by multiplying: bt / heads and
+// head / group as 64-bit divisions run on the vector unit and cost the int8 t128 and the causal sm128, both at their register limit, a spilled VGPR or three.
+// heads_magic = floor(2^64 / heads) + 1 (2^64 / heads for a power of two) gives bt / heads = mulhi(bt, heads_magic) exactly for bt < 2^57 (heads <= 128: the
+// error term bt * heads stays below 2^64); group_magic = floor(2^32 / group) + 1 gives head / group = head * group_magic >> 32 for head < 128, group <= 256.
+struct BmmTok {
+    uint64_t heads_magic;
+    int64_t group_magic, heads, a_head, a_pitch, b_seq, b_head, b_pitch, o_head, o_pitch;
+};
+struct BmmAt {   // one batch entry: its first a and b rows, the element offset of its first output row, the three row pitches
+    const int8_t *a, *b;
+    int64_t obase, pa, pb, po;
+};
+template <bool KN, bool GROUPED, bool TOKEN>
+__device__ __forceinline__ BmmAt bmm_entry(const int8_t *a, const int8_t *b, int64_t bt, int64_t group, int64_t M, int64_t N, int64_t K, const BmmTok &tok)
+{
+    if constexpr (!TOKEN) {
+        return {a + bt * M * K, bmm_b_entry<GROUPED>(b, bt, group, N * K), bt * M * N, K, KN ? N : K, N};
+    } else {
+        const int64_t seq = (int64_t)__umul64hi((uint64_t)bt, tok.heads_magic), head = bt - seq * tok.heads, first = bt - head;   // first: the sequence's entry 0
+        return {a + first * M * K + head * tok.a_head, b + seq * tok.b_seq + ((head * tok.group_magic) >> 32) * tok.b_head, first * M * N + head * tok.o_head, tok.a_pitch, tok.b_pitch, tok.o_pitch};
+    }
+}
+
 // The output images (t128's staging image, sm128's int8 image): rows of RB bytes, 16-B chunk c of image row ir is stored at c ^ (ir & (RB / 16 - 1)).
 template <int RB> __device__ __forceinline__ int bmm_stage_off(int ir, int c) { return ir * RB + ((c ^ (ir & (RB / 16 - 1))) << 4); }
 
@@ -162,9 +192,9 @@ template <bool KN> __device__ __forceinline__ void bmm_mma_step(const char *xs, 
 // load covers 8 rows of 128 contiguous bytes.  Its B image is [n row][16-B chunks of k] with chunk index ^= ((row >> 1) & 7) ^ (row >> 4): the second term is constant
 // over the 16 rows of a fragment read (the reads stay conflict-free) and spreads the dword writes of a 32-lane half -- 8 nc x 4 (kg & 3), one kg >> 2 -- over all 32 banks.
 // The transpose's registers do not fit the int8 kind's 3 blocks per CU without spilling: KN runs 2 blocks per CU for every kind.
-template <int KIND, bool KN = false, bool GROUPED = false>
+template <int KIND, bool KN = false, bool GROUPED = false, bool TOKEN = false>
 __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8_t128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
-                                                   int64_t K, int64_t tiles_m, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec)
+                                                   int64_t K, int64_t tiles_m, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec, BmmTok tok)
 {
     constexpr int EB = BmmOut<KIND>::kBytes, RB = BMM_TN * EB, NC = RB / 16;   // staging image: 64 rows of RB bytes = NC 16-B chunks
     static_assert(64 * RB <= 2 * BMM_TM * BMM_TK, "the staging image reuses the operand tiles");
@@ -177,7 +207,7 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / per_batch, r = id - bt * per_batch;
         const int64_t m0 = (r / tiles_n) * BMM_TM, n0 = (r % tiles_n) * BMM_TN;
-        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, N * K);
+        const BmmAt at = bmm_entry<KN, GROUPED, TOKEN>(a, b, bt, group, M, N, K, tok);
 
         // K step = [128 rows][128 B] of each operand; thread tid moves chunks tid + 256 i (row = chunk >> 3, 16-B column = chunk & 7) into bmm_tile_off's image.
         v4i px[4], pw[4];
@@ -185,9 +215,9 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = tid + 256 * i, row = c >> 3, ch = c & 7;
-                px[i] = load16_guarded(ab, K, m0 + row, M, k0 + ch * 16, K, fast);
-                if constexpr (KN) pw[i] = load16_guarded(bb, N, k0 + 4 * (tid >> 3) + i, K, n0 + 16 * (tid & 7), N, fast);
-                else pw[i] = load16_guarded(bb, K, n0 + row, N, k0 + ch * 16, K, fast);
+                px[i] = load16_guarded(at.a, at.pa, m0 + row, M, k0 + ch * 16, K, fast);
+                if constexpr (KN) pw[i] = load16_guarded(at.b, at.pb, k0 + 4 * (tid >> 3) + i, K, n0 + 16 * (tid & 7), N, fast);
+                else pw[i] = load16_guarded(at.b, at.pb, n0 + row, N, k0 + ch * 16, K, fast);
             }
         };
         v4i acc[4][4];   // [m tile][n tile] of the wave's 64 x 64
@@ -225,7 +255,6 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
 
         // Epilogue in two passes of 32 rows per wave.  Image row ir = wm * 32 + (row within the pass) holds output row
         // m0 + wm * 64 + 32 p + (ir & 31); 16-B chunk c of a row is stored at c ^ (ir & (NC - 1)).
-        const int64_t obase = bt * M * N;
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
 #pragma unroll
@@ -243,7 +272,7 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
                 const int idx = tid + 256 * i, ir = idx / NC, c = idx % NC;
                 const v4i v = *(const v4i *)(lds + bmm_stage_off<RB>(ir, c));
                 const int64_t m = m0 + (ir >> 5) * 64 + 32 * p + (ir & 31), n = n0 + c * (16 / EB);
-                if (m < M && n < N) bmm_store_chunk<EB>(out, obase + m * N + n, v, N - n, vec);
+                if (m < M && n < N) bmm_store_chunk<EB>(out, at.obase + m * at.po + n, v, N - n, vec);
             }
             __syncthreads();
         }
@@ -252,9 +281,9 @@ __global__ void __launch_bounds__(256, KIND == ASQ_BMM_S8 && !KN ? 3 : 2) bmm_i8
 
 constexpr int BMM_NT = 2;   // 16-column MFMA tiles per bmm_i8_m16 block
 
-template <int KIND, bool GROUPED = false>
+template <int KIND, bool GROUPED = false, bool TOKEN = false>
 __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
-                                                  int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4)
+                                                  int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4, BmmTok tok)
 {
     __shared__ v4i red[4][BMM_NT][64];   // each wave's partial sums, lane-linear
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -263,17 +292,17 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / tiles_n, n0 = (id - bt * tiles_n) * (16 * BMM_NT);
-        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, N * K);
+        const BmmAt at = bmm_entry<false, GROUPED, TOKEN>(a, b, bt, group, M, N, K, tok);
         v4i acc[BMM_NT];
 #pragma unroll
         for (int j = 0; j < BMM_NT; ++j) acc[j] = (v4i){0, 0, 0, 0};
         // MFMA fragments straight from memory: lane = row t16 (of A: the token; of B: the column n0 + 16 j + t16), 16 k-bytes at 16 q16 of the K step
         for (int64_t ks = wave; ks < nks; ks += 4) {
             const int64_t k = ks * 64 + q16 * 16;
-            const v4i fx = load16_guarded(ab, K, t16, M, k, K, fast);
+            const v4i fx = load16_guarded(at.a, at.pa, t16, M, k, K, fast);
             v4i fw[BMM_NT];
 #pragma unroll
-            for (int j = 0; j < BMM_NT; ++j) fw[j] = load16_guarded(bb, K, n0 + 16 * j + t16, N, k, K, fast);
+            for (int j = 0; j < BMM_NT; ++j) fw[j] = load16_guarded(at.b, at.pb, n0 + 16 * j + t16, N, k, K, fast);
 #pragma unroll
             for (int j = 0; j < BMM_NT; ++j) acc[j] = MmaI8x16::mma(fw[j], fx, acc[j]);
         }
@@ -284,7 +313,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
             const int j = wave;
             const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
             const int64_t m = t16, n = n0 + 16 * j + 4 * q16;
-            if (m < M && n < N) bmm_store4<KIND>(out, bt * M * N + m * N + n, s, n, N, alpha, vec4);
+            if (m < M && n < N) bmm_store4<KIND>(out, at.obase + m * at.po + n, s, n, N, alpha, vec4);
         }
         __syncthreads();   // red is rewritten by the next tile of a grid-stride loop
     }
@@ -295,20 +324,20 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
 // lane (t16, q16) is then row t16, column n0 + 4 (4 q16 + reg) + e, so the four MFMAs' registers `reg` are 4 consecutive columns: red[wave][reg][lane].
 constexpr int BMM_KN_TN = 64;
 
-__device__ __forceinline__ uint32_t load4_kn(const int8_t *base, int64_t N, int64_t k, int64_t K, int64_t n, bool fast)
+__device__ __forceinline__ uint32_t load4_kn(const int8_t *base, int64_t ld, int64_t N, int64_t k, int64_t K, int64_t n, bool fast)
 {
     if (k >= K || n >= N) return 0;
-    const int8_t *p = base + k * N + n;
-    if (fast) return *(const uint32_t *)p;   // N % 16 == 0, n % 4 == 0, base 16-B aligned
+    const int8_t *p = base + k * ld + n;
+    if (fast) return *(const uint32_t *)p;   // N % 16 == 0 (so is the row pitch ld), n % 4 == 0, base 16-B aligned
     uint32_t w = 0;
     for (int i = 0; i < 4; ++i)
         if (n + i < N) w |= (uint32_t)(uint8_t)p[i] << (8 * i);
     return w;
 }
 
-template <int KIND, bool GROUPED = false>
+template <int KIND, bool GROUPED = false, bool TOKEN = false>
 __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
-                                                    int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4)
+                                                    int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4, BmmTok tok)
 {
     __shared__ v4i red[4][4][64];   // each wave's partial sums: [wave][accumulator register][lane], the 4 ints are 4 consecutive columns
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -317,16 +346,16 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / tiles_n, n0 = (id - bt * tiles_n) * BMM_KN_TN;
-        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, K * N);
+        const BmmAt at = bmm_entry<true, GROUPED, TOKEN>(a, b, bt, group, M, N, K, tok);
         v4i acc[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[e] = (v4i){0, 0, 0, 0};
         for (int64_t ks = wave; ks < nks; ks += 4) {
             const int64_t k = ks * 64 + q16 * 16;
-            const v4i fx = load16_guarded(ab, K, t16, M, k, K, fast);
+            const v4i fx = load16_guarded(at.a, at.pa, t16, M, k, K, fast);
             uint32_t rows[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) rows[r] = load4_kn(bb, N, k + r, K, n0 + 4 * t16, fast);
+            for (int r = 0; r < 16; ++r) rows[r] = load4_kn(at.b, at.pb, N, k + r, K, n0 + 4 * t16, fast);
             v4i fw[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -345,7 +374,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
             const int j = wave;
             const v4i s = red[0][j][lane] + red[1][j][lane] + red[2][j][lane] + red[3][j][lane];
             const int64_t m = t16, n = n0 + 16 * q16 + 4 * j;
-            if (m < M && n < N) bmm_store4<KIND>(out, bt * M * N + m * N + n, s, n, N, alpha, vec4);
+            if (m < M && n < N) bmm_store4<KIND>(out, at.obase + m * at.po + n, s, n, N, alpha, vec4);
         }
         __syncthreads();   // red is rewritten by the next tile of a grid-stride loop
     }
@@ -362,9 +391,9 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
 // read) and their outputs zero-filled; only tiles cut by the diagonal or by N take the masked epilogue.
 constexpr float SM_LOG2E = 1.44269502162933349609375f, SM_MAGIC = 12582912.0f;   // 1.5 * 2^23: the low mantissa bits of (x + SM_MAGIC) are rne(x)
 
-template <bool CAUSAL, bool FAST, bool GROUPED = false>
+template <bool CAUSAL, bool FAST, bool GROUPED = false, bool TOKEN = false>   // TOKEN: a and b only; the probabilities stay dense for P . V
 __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, int8_t *__restrict__ out, int64_t M, int64_t N,
-                                                      int64_t K, int64_t tiles_m, int64_t total, int64_t group, float alpha, bool vec)
+                                                      int64_t K, int64_t tiles_m, int64_t total, int64_t group, float alpha, bool vec, BmmTok tok)
 {
     __shared__ __attribute__((aligned(16))) char lds[3 * BMM_TM * BMM_TK];   // [A tile | B tile | output image 128 x 128 B, between the passes the rows' partials]
     char *const xs = lds, *const ws = lds + BMM_TM * BMM_TK, *const st = lds + 2 * BMM_TM * BMM_TK;
@@ -377,7 +406,7 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
 
     for (int64_t id = xcd_remap(blockIdx.x, gridDim.x); id < total; id += gridDim.x) {
         const int64_t bt = id / tiles_m, m0 = (id - bt * tiles_m) * BMM_TM;
-        const int8_t *const ab = a + bt * M * K, *const bb = bmm_b_entry<GROUPED>(b, bt, group, N * K);
+        const BmmAt at = bmm_entry<false, GROUPED, TOKEN>(a, b, bt, group, M, N, K, tok);
         const int64_t obase = bt * M * N, mlast = (m0 + BMM_TM < M ? m0 + BMM_TM : M) - 1;
         auto visible = [&](int64_t m) -> int64_t {   // keys 0 .. visible(m) - 1 are seen by query m
             if (!CAUSAL) return N;
@@ -406,14 +435,14 @@ __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict_
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int64_t ra = m0 + row + 32 * i < M ? m0 + row + 32 * i : M - 1, rb = n0 + row + 32 * i < n_end ? n0 + row + 32 * i : n_end - 1;
-                    if (with_a) px[i] = *(const v4i *)(ab + ra * K + kc);
-                    pw[i] = *(const v4i *)(bb + rb * K + kc);
+                    if (with_a) px[i] = *(const v4i *)(at.a + ra * at.pa + kc);
+                    pw[i] = *(const v4i *)(at.b + rb * at.pb + kc);
                 }
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if (with_a) px[i] = load16_guarded(ab, K, m0 + row + 32 * i, M, k, K, false);
-                    pw[i] = load16_guarded(bb, K, n0 + row + 32 * i, n_end, k, K, false);
+                    if (with_a) px[i] = load16_guarded(at.a, at.pa, m0 + row + 32 * i, M, k, K, false);
+                    pw[i] = load16_guarded(at.b, at.pb, n0 + row + 32 * i, n_end, k, K, false);
                 }
             }
         };
@@ -567,56 +596,80 @@ static inline bool bmm_narrow(int64_t M) { return M <= 16; }
 
 static inline int64_t bmm_grid(int64_t total) { return total < (int64_t(1) << 30) ? total : (int64_t(1) << 30); }
 
-template <int KIND, bool KN, bool GROUPED>   // KN: b is [batch, K, N]; GROUPED: group > 1 batch entries per b (bmm_b_entry)
-static int launch_bmm_as(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
-{
-    constexpr int EB = BmmOut<KIND>::kBytes, NARROW_TN = KN ? BMM_KN_TN : 16 * BMM_NT;
-    const bool fast = (K % 16 == 0) && (!KN || N % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
-    if (bmm_narrow(M)) {
-        const int64_t tiles_n = (N + NARROW_TN - 1) / NARROW_TN, total = batch * tiles_n;
-        const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
-        const auto kernel = KN ? bmm_i8_m16kn<KIND, GROUPED> : bmm_i8_m16<KIND, GROUPED>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, group, alpha, fast, vec4);
-    } else {
-        const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
-        const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
-        hipLaunchKernelGGL((bmm_i8_t128<KIND, KN, GROUPED>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, group,
-                           alpha, fast, vec);
-    }
-    return asq_after_launch(s, "asq_bmm_i8");
-}
-template <int KIND, bool KN> static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
-{
-    return group > 1 ? launch_bmm_as<KIND, KN, true>(a, b, out, batch, group, M, N, K, alpha, s) : launch_bmm_as<KIND, KN, false>(a, b, out, batch, group, M, N, K, alpha, s);
-}
-
-template <bool GROUPED>
-static int launch_bmm_softmax_as(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
-{
-    const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0), vec = (N % 16 == 0) && (((uintptr_t)out & 15) == 0);
-    const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, total = batch * tiles_m;
-    const auto kernel = causal ? (fast ? bmm_i8_sm128<true, true, GROUPED> : bmm_i8_sm128<true, false, GROUPED>)
-                               : (fast ? bmm_i8_sm128<false, true, GROUPED> : bmm_i8_sm128<false, false, GROUPED>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, total, group, alpha, vec);
-    return asq_after_launch(s, "asq_bmm_i8");
-}
-static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, int64_t group, int64_t M, int64_t N, int64_t K, float alpha, bool causal, hipStream_t s)
-{
-    return group > 1 ? launch_bmm_softmax_as<true>(a, b, out, batch, group, M, N, K, alpha, causal, s) : launch_bmm_softmax_as<false>(a, b, out, batch, group, M, N, K, alpha, causal, s);
-}
-
 // out_kind = a base kind in the low two bits plus flags.  Valid: 0, 1, 2; ASQ_BMM_B_KN | {0, 1, 2} (128 .. 130); ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]
-// (18, 50); each of the eight with ASQ_BMM_B_GROUP(r), r - 1 in bits 16 .. 23.  Every other value, negative ones included, is not.
+// (18, 50); each of the eight with ASQ_BMM_B_GROUP(r), r - 1 in bits 16 .. 23; each of those with a non-empty subset of ASQ_BMM_A_TOKEN / _B_TOKEN / _OUT_TOKEN and
+// ASQ_BMM_HEADS(h), h - 1 in bits 24 .. 30 and not 0 (the flags and the field come together or not at all; no _OUT_TOKEN on the softmax kinds).  Every other
+// value, negative ones included, is not.
 struct BmmKind {
-    int base, group;
-    bool kn, softmax, causal, valid;
+    int base, group, heads;   // heads: 0 without a token flag
+    bool kn, softmax, causal, a_tok, b_tok, o_tok, valid;
 };
 static inline BmmKind bmm_decode(int out_kind)
 {
-    const int group_bits = out_kind & ASQ_BMM_B_GROUP(256), base = out_kind & 3, flags = out_kind & ~(3 | group_bits);
+    constexpr int TOKEN_BITS = ASQ_BMM_A_TOKEN | ASQ_BMM_B_TOKEN | ASQ_BMM_OUT_TOKEN;
+    const int group_bits = out_kind & ASQ_BMM_B_GROUP(256), token_bits = out_kind & TOKEN_BITS, heads_bits = out_kind & ASQ_BMM_HEADS(128), base = out_kind & 3;
+    const int flags = out_kind & ~(3 | group_bits | token_bits | heads_bits);
     const bool kn = flags == ASQ_BMM_B_KN, softmax = flags == ASQ_BMM_SOFTMAX || flags == (ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL);
-    return {base, (group_bits >> 16) + 1, kn, softmax, softmax && (flags & ASQ_BMM_CAUSAL) != 0,
-            softmax ? base == ASQ_BMM_S8 : (kn || flags == 0) && base <= ASQ_BMM_S8};
+    const bool o_tok = (token_bits & ASQ_BMM_OUT_TOKEN) != 0, token_ok = (token_bits != 0) == (heads_bits != 0) && !(softmax && o_tok);
+    return {base, (group_bits >> 16) + 1, token_bits ? (heads_bits >> 24) + 1 : 0, kn, softmax, softmax && (flags & ASQ_BMM_CAUSAL) != 0,
+            (token_bits & ASQ_BMM_A_TOKEN) != 0, (token_bits & ASQ_BMM_B_TOKEN) != 0, o_tok,
+            token_ok && (softmax ? base == ASQ_BMM_S8 : (kn || flags == 0) && base <= ASQ_BMM_S8)};
+}
+// batch entries per b and per sequence agree with the batch and with each other
+static inline bool bmm_heads_ok(const BmmKind &kind, int64_t batch)
+{
+    return kind.heads == 0 || (batch % kind.heads == 0 && kind.heads % kind.group == 0 && batch < (int64_t(1) << 57));   // (2^57: BmmTok's heads_magic; no such batch fits a memory)
+}
+
+// The strides of bmm_entry: a sequence's b block, then per operand a head's start within its sequence and the row pitch, token-major or dense.
+static inline BmmTok bmm_tok(const BmmKind &kind, int64_t M, int64_t N, int64_t K)
+{
+    const int64_t h = kind.heads, hb = h / kind.group, bcols = kind.kn ? N : K;   // b's rows are bcols long
+    return {~uint64_t(0) / (uint64_t)h + 1, (int64_t)((uint64_t(1) << 32) / (uint64_t)kind.group + 1), h, kind.a_tok ? K : M * K, kind.a_tok ? h * K : K, hb * N * K, kind.b_tok ? bcols : N * K, kind.b_tok ? hb * bcols : bcols,
+            kind.o_tok ? N : M * N, kind.o_tok ? h * N : N};
+}
+
+template <int KIND, bool KN, bool GROUPED, bool TOKEN>   // KN: b is [batch, K, N]; GROUPED: group > 1 batch entries per b (bmm_b_entry); TOKEN: bmm_entry's strides
+static int launch_bmm_as(const int8_t *a, const int8_t *b, void *out, int64_t batch, const BmmKind &kind, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    constexpr int EB = BmmOut<KIND>::kBytes, NARROW_TN = KN ? BMM_KN_TN : 16 * BMM_NT;
+    const bool fast = (K % 16 == 0) && (!KN || N % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
+    const int64_t group = kind.group;
+    const BmmTok tok = TOKEN ? bmm_tok(kind, M, N, K) : BmmTok{};
+    if (bmm_narrow(M)) {
+        const int64_t tiles_n = (N + NARROW_TN - 1) / NARROW_TN, total = batch * tiles_n;
+        const bool vec4 = (N % 4 == 0) && (((uintptr_t)out & (4 * EB - 1)) == 0);
+        const auto kernel = KN ? bmm_i8_m16kn<KIND, GROUPED, TOKEN> : bmm_i8_m16<KIND, GROUPED, TOKEN>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_n, total, group, alpha, fast, vec4, tok);
+    } else {
+        const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, tiles_n = (N + BMM_TN - 1) / BMM_TN, total = batch * tiles_m * tiles_n;
+        const bool vec = ((N * EB) % 16 == 0) && (((uintptr_t)out & 15) == 0);
+        hipLaunchKernelGGL((bmm_i8_t128<KIND, KN, GROUPED, TOKEN>), dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, tiles_n, total, group,
+                           alpha, fast, vec, tok);
+    }
+    return asq_after_launch(s, "asq_bmm_i8");
+}
+template <int KIND, bool KN> static int launch_bmm(const int8_t *a, const int8_t *b, void *out, int64_t batch, const BmmKind &kind, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    if (kind.heads) return launch_bmm_as<KIND, KN, false, true>(a, b, out, batch, kind, M, N, K, alpha, s);
+    return kind.group > 1 ? launch_bmm_as<KIND, KN, true, false>(a, b, out, batch, kind, M, N, K, alpha, s) : launch_bmm_as<KIND, KN, false, false>(a, b, out, batch, kind, M, N, K, alpha, s);
+}
+
+template <bool GROUPED, bool TOKEN>
+static int launch_bmm_softmax_as(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, const BmmKind &kind, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    const bool fast = (K % 16 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 15) == 0), vec = (N % 16 == 0) && (((uintptr_t)out & 15) == 0);
+    const int64_t tiles_m = (M + BMM_TM - 1) / BMM_TM, total = batch * tiles_m, group = kind.group;
+    const BmmTok tok = TOKEN ? bmm_tok(kind, M, N, K) : BmmTok{};
+    const auto kernel = kind.causal ? (fast ? bmm_i8_sm128<true, true, GROUPED, TOKEN> : bmm_i8_sm128<true, false, GROUPED, TOKEN>)
+                                    : (fast ? bmm_i8_sm128<false, true, GROUPED, TOKEN> : bmm_i8_sm128<false, false, GROUPED, TOKEN>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)bmm_grid(total)), dim3(256), 0, s, a, b, out, M, N, K, tiles_m, total, group, alpha, vec, tok);
+    return asq_after_launch(s, "asq_bmm_i8");
+}
+static int launch_bmm_softmax(const int8_t *a, const int8_t *b, int8_t *out, int64_t batch, const BmmKind &kind, int64_t M, int64_t N, int64_t K, float alpha, hipStream_t s)
+{
+    if (kind.heads) return launch_bmm_softmax_as<false, true>(a, b, out, batch, kind, M, N, K, alpha, s);
+    return kind.group > 1 ? launch_bmm_softmax_as<true, false>(a, b, out, batch, kind, M, N, K, alpha, s) : launch_bmm_softmax_as<false, false>(a, b, out, batch, kind, M, N, K, alpha, s);
 }
 
 static inline bool bmm_mul(int64_t x, int64_t y, int64_t &r) { return !__builtin_mul_overflow(x, y, &r); }
@@ -628,7 +681,7 @@ using namespace asq;
 extern "C" const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind)
 {
     const BmmKind kind = bmm_decode(out_kind);
-    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || !kind.valid || batch % kind.group != 0) return "none";
+    if (batch <= 0 || M <= 0 || N <= 0 || K < 0 || !kind.valid || batch % kind.group != 0 || !bmm_heads_ok(kind, batch)) return "none";
     if (kind.softmax) return "sm128";
     if (kind.kn) return bmm_narrow(M) ? "m16kn" : "t128kn";
     return bmm_narrow(M) ? "m16" : "t128";
@@ -646,16 +699,17 @@ extern "C" int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_k
                 ASQ_ERR_DIM, "asq_bmm_i8: size overflows 64 bits (batch=%lld M=%lld N=%lld K=%lld)", (long long)batch, (long long)M, (long long)N, (long long)K);
     ASQ_REQUIRE(kind.valid, ASQ_ERR_DTYPE, "asq_bmm_i8: bad out_kind %d", out_kind);
     ASQ_REQUIRE(batch % kind.group == 0, ASQ_ERR_DIM, "asq_bmm_i8: batch=%lld is no multiple of the b group size %d", (long long)batch, kind.group);
+    ASQ_REQUIRE(bmm_heads_ok(kind, batch), ASQ_ERR_DIM, "asq_bmm_i8: batch=%lld, %d heads per sequence (ASQ_BMM_HEADS) and the b group size %d do not divide", (long long)batch,
+                kind.heads, kind.group);
     if (bmn == 0) return ASQ_OK;
     ASQ_REQUIRE(out != nullptr, ASQ_ERR_NULL, "asq_bmm_i8: NULL out");
     ASQ_REQUIRE(K == 0 || (a != nullptr && b != nullptr), ASQ_ERR_NULL, "asq_bmm_i8: NULL a / b");
     ASQ_REQUIRE(kind.base == ASQ_BMM_S8 || ((uintptr_t)out & 3) == 0, ASQ_ERR_ALIGN, "asq_bmm_i8: out misaligned for its element");
     hipStream_t s = (hipStream_t)stream;
-    const int64_t g = kind.group;
-    if (kind.softmax) return launch_bmm_softmax(a, b, (int8_t *)out, batch, g, M, N, K, alpha, kind.causal, s);
+    if (kind.softmax) return launch_bmm_softmax(a, b, (int8_t *)out, batch, kind, M, N, K, alpha, s);
     switch (kind.base) {
-    case ASQ_BMM_S32: return kind.kn ? launch_bmm<ASQ_BMM_S32, true>(a, b, out, batch, g, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S32, false>(a, b, out, batch, g, M, N, K, alpha, s);
-    case ASQ_BMM_F32: return kind.kn ? launch_bmm<ASQ_BMM_F32, true>(a, b, out, batch, g, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_F32, false>(a, b, out, batch, g, M, N, K, alpha, s);
-    default: return kind.kn ? launch_bmm<ASQ_BMM_S8, true>(a, b, out, batch, g, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S8, false>(a, b, out, batch, g, M, N, K, alpha, s);
+    case ASQ_BMM_S32: return kind.kn ? launch_bmm<ASQ_BMM_S32, true>(a, b, out, batch, kind, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S32, false>(a, b, out, batch, kind, M, N, K, alpha, s);
+    case ASQ_BMM_F32: return kind.kn ? launch_bmm<ASQ_BMM_F32, true>(a, b, out, batch, kind, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_F32, false>(a, b, out, batch, kind, M, N, K, alpha, s);
+    default: return kind.kn ? launch_bmm<ASQ_BMM_S8, true>(a, b, out, batch, kind, M, N, K, alpha, s) : launch_bmm<ASQ_BMM_S8, false>(a, b, out, batch, kind, M, N, K, alpha, s);
     }
 }

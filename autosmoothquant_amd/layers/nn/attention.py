@@ -4,7 +4,8 @@
     O = sat_i8(rne(v_scale / (127 * out_scale) * (P . v)))               pv_bmm's alpha on ops.bmm_i8_kn: v is read as it is stored, [batch, Sk, d]
 
 Grouped-query attention (q [..., Hq, Sq, d] over k, v [..., Hkv, Sk, d], Hq = r * Hkv) takes the same two launches and never expands k or v: the r heads of a
-group become rows of one product, or share b through ASQ_BMM_B_GROUP (forward, _forward_gqa).
+group become rows of one product, or share b through ASQ_BMM_B_GROUP (forward, _forward_gqa).  With layout="bshd" the operands are [B, S, H, d], as the
+q/k/v projections write them, a token-by-token KV cache holds them and o_proj reads them: the same two launches on token-major addresses (_forward_bshd).
 
 The reference stops at the two matmul modules and leaves the softmax between them to the caller (fp32 scores, eager softmax, a cast);
 here the first product carries it as its epilogue.  The state dict is the two scalar buffers ``qk_bmm.a`` and ``pv_bmm.a`` (host-pinned,
@@ -33,12 +34,17 @@ class Int8Attention(torch.nn.Module):
         mod.pv_bmm = BMM_S8T_S8N_S8T._with_alpha(v_scale / (127 * out_scale))
         return mod
 
-    def forward(self, q, k, v):
+    def forward(self, q, k, v, layout="bhsd"):
         """q int8 [..., Sq, d], k and v int8 [..., Sk, d] with equal leading dims (flattened to the batch) -> int8 [..., Sq, d].
         Causal masking is bottom-right aligned (query m sees keys n <= m + Sk - Sq), so a decode step with a KV cache sees every key.
         P . V reads v where it is (ASQ_BMM_B_KN): no transposed copy; only a non-contiguous v is made contiguous first.
         Grouped-query attention: q [..., Hq, Sq, d] over k and v [..., Hkv, Sk, d] with equal dims before the heads and Hq = r * Hkv; query head h
-        uses KV head h // r.  K and V are never expanded: see _forward_gqa."""
+        uses KV head h // r.  K and V are never expanded: see _forward_gqa.
+        layout="bshd": q [B, Sq, Hq, d], k and v [B, Sk, Hkv, d] -> [B, Sq, Hq, d], the layout q/k/v projections write and o_proj reads; see _forward_bshd."""
+        if layout == "bshd":
+            return self._forward_bshd(q, k, v)
+        if layout != "bhsd":
+            raise ValueError(f"layout must be 'bhsd' or 'bshd', got {layout!r}")
         if q.dim() < 2 or k.shape != v.shape or q.shape[-1] != k.shape[-1]:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
         lead, sq, d, sk = q.shape[:-2], q.shape[-2], q.shape[-1], k.shape[-2]
@@ -66,3 +72,27 @@ class Int8Attention(torch.nn.Module):
             return ops.bmm_i8_kn(p, v3, torch.int8, pv_alpha)
         p = ops.bmm_i8_softmax_q8(q.reshape(-1, sq, d), k3, qk_alpha, True, b_group=r)
         return ops.bmm_i8_kn(p, v3, torch.int8, pv_alpha, b_group=r)
+
+    def _forward_bshd(self, q, k, v):
+        """q [B, Sq, Hq, d], k and v [B, Sk, Hkv, d], Hq = r * Hkv, each contiguous -> [B, Sq, Hq, d]: the two launches read the projections where they lie and
+        write o_proj's input in place (ASQ_BMM_A_TOKEN / _B_TOKEN / _OUT_TOKEN), bit-identical to the head-major forward on permuted copies.  No operand is
+        copied; only P, [B * Hq, Sq, Sk], is dense.
+        Sq > 1, or r == 1: the heads are batch entries, sharing K / V through b_group = r when r > 1.
+        Sq == 1 and r > 1 (a decode step): the r heads of a group are the r dense rows of q.view(B * Hkv, r, d), folded as in _forward_gqa -- only K and V are
+        token-major (heads = Hkv, no group), the causal flag is dropped, and the dense [B * Hkv, r, d] result is [B, 1, Hq, d].
+        With B == 1 the first Sk tokens of a preallocated [1, Smax, Hkv, d] cache are contiguous: a single-sequence decode step takes cache[:, :Sk] as it is."""
+        if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3] or k.shape[2] == 0 or q.shape[2] % k.shape[2] != 0:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} must be [B, Sq, Hq, d], k {tuple(k.shape)} and v {tuple(v.shape)} [B, Sk, Hkv, d] with Hq a multiple of Hkv")
+        bsz, sq, hq, d = q.shape
+        hkv = k.shape[2]
+        r = hq // hkv
+        qk_alpha, pv_alpha = self.qk_bmm._alpha(), self.pv_bmm._alpha()
+        if not q.is_contiguous():   # (k and v: the ops look; q is viewed below)
+            raise ValueError("q, k and v must be contiguous in the bshd layout (make a slice of a fused q|k|v buffer contiguous first)")
+        if hkv == 1 and (hq == 1 or sq == 1):   # one head per sequence is the dense layout itself: [B, S, 1, d] = [B, S, d]
+            return self.forward(q.view(bsz, hq, sq, d), k.reshape(bsz, 1, -1, d), v.reshape(bsz, 1, -1, d)).view(bsz, sq, hq, d)
+        if sq == 1 and r > 1:
+            p = ops.bmm_i8_softmax_q8(q.view(bsz * hkv, r, d), k, qk_alpha, False, heads=hkv)
+            return ops.bmm_i8_kn(p, v, torch.int8, pv_alpha, heads=hkv).view(bsz, 1, hq, d)
+        p = ops.bmm_i8_softmax_q8(q, k, qk_alpha, self.causal, b_group=r)
+        return ops.bmm_i8_kn(p, v, torch.int8, pv_alpha, b_group=r, out_token=True, heads=hq)

@@ -946,17 +946,22 @@ _BMM_KIND = {torch.int32: L.ASQ_BMM_S32, torch.float32: L.ASQ_BMM_F32, torch.int
 _BMM_DTYPE = {code: dt for dt, code in _BMM_KIND.items()}
 
 
-def _bmm(a, b, alpha, out_kind, flags=0, b_group=1):
+def _bmm(a, b, alpha, out_kind, flags=0, b_group=1, out_token=False, heads=None):
     """The checks, the allocation and the asq_bmm_i8 call of the three ops below: out_kind is a dtype or a plain ASQ_BMM_S32 / _F32 / _S8 code, flags the
     ASQ_BMM_* flags of the call.  With ASQ_BMM_B_KN among them b is [B, K, N] and the flag may be set on out_kind as well.  b_group = r (1 .. 256): b has
-    B / r entries and entry i of a uses b[i // r] (ASQ_BMM_B_GROUP)."""
+    B / r entries and entry i of a uses b[i // r] (ASQ_BMM_B_GROUP).  A 4-D a or b, or out_token, is token-major (ASQ_BMM_*_TOKEN): see _bmm_token."""
     kn = bool(flags & L.ASQ_BMM_B_KN)
     _dev(a, "a"), _dev(b, "b")
     if a.dtype != torch.int8 or b.dtype != torch.int8:
         raise RuntimeError(f"expected int8 a and b, got {a.dtype} and {b.dtype}")
     if not (isinstance(b_group, int) and 1 <= b_group <= 256):
         raise ValueError(f"b_group must be an int in 1 .. 256, got {b_group!r} (a {tuple(a.shape)}, b {tuple(b.shape)})")
-    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] * b_group or a.shape[2] != b.shape[1 if kn else 2]:
+    token = a.dim() == 4 or b.dim() == 4 or bool(out_token)
+    if token:
+        flags, B, M, N, K, out_shape = _bmm_token(a, b, kn, flags, b_group, bool(out_token), heads)
+    elif heads is not None:
+        raise ValueError(f"heads={heads!r} goes with a token-major operand (a 4-D a or b, or out_token=True): a {tuple(a.shape)}, b {tuple(b.shape)}")
+    elif a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] * b_group or a.shape[2] != b.shape[1 if kn else 2]:
         raise ValueError(f"shape mismatch: a {tuple(a.shape)} must be [B, M, K] and b {tuple(b.shape)} {'[B, K, N]' if kn else '[B, N, K]'}"
                          + (f" with B / {b_group} entries (b_group)" if b_group != 1 else ""))
     if b_group != 1:
@@ -967,35 +972,83 @@ def _bmm(a, b, alpha, out_kind, flags=0, b_group=1):
     if kind not in _BMM_DTYPE:
         raise ValueError(f"out_kind must be torch.int32, torch.float32 or torch.int8 (or an ASQ_BMM_* code), got {out_kind!r}")
     dev = _same_device(a, b)
-    B, M, K = a.shape
-    N = b.shape[2 if kn else 1]
-    out = torch.empty((B, M, N), dtype=_BMM_DTYPE[kind], device=dev)
+    if not token:
+        B, M, K = a.shape
+        N = b.shape[2 if kn else 1]
+        out_shape = (B, M, N)
+    out = torch.empty(out_shape, dtype=_BMM_DTYPE[kind], device=dev)
     with _on(dev):
         L.check(L.lib().asq_bmm_i8(a.data_ptr(), b.data_ptr(), out.data_ptr(), kind | flags, B, M, N, K, float(alpha), _stream(a)), "asq_bmm_i8")
     return out
 
 
-def bmm_i8(a, b, out_kind, alpha=1.0, b_group=1):
+def _bmm_token(a, b, kn, flags, r, out_token, heads):
+    """The token-major call: a 4-D a is [S, M, h, K] (ASQ_BMM_A_TOKEN), a 4-D b is [S, N, h / r, K] -- [S, K, h / r, N] when kn -- (ASQ_BMM_B_TOKEN), out_token
+    asks for out [S, M, h, N] (ASQ_BMM_OUT_TOKEN); a 3-D operand is dense over the S * h batch entries (b: S * h / r), entry i being head i % h of sequence
+    i // h.  h comes from a 4-D a, otherwise from heads.  -> (flags with the token bits and ASQ_BMM_HEADS(h), batch, M, N, K, out's shape)."""
+    def bad(why):
+        return ValueError(f"{why}: a {tuple(a.shape)}, b {tuple(b.shape)}, b_group {r}, heads {heads!r}")
+    ad, bd = a.dim(), b.dim()
+    if ad not in (3, 4) or bd not in (3, 4):
+        raise bad("shape mismatch: a and b must be 3-D (dense) or 4-D (token-major)")
+    if flags & L.ASQ_BMM_SOFTMAX and out_token:
+        raise bad("the softmax kinds write a dense [B, M, N], out_token is not available")
+    if ad == 4:
+        S, M, h, K = a.shape
+        flags |= L.ASQ_BMM_A_TOKEN
+        if heads is not None and heads != h:
+            raise bad("heads disagrees with the heads of the 4-D a")
+    else:
+        h = heads
+        if not isinstance(h, int) or isinstance(h, bool) or h < 1 or a.shape[0] % h != 0:
+            raise bad("heads must be given as an int that divides a's batch when a is 3-D")
+        S, M, K = a.shape[0] // h, a.shape[1], a.shape[2]
+    if not 2 <= h <= 128:
+        raise bad(f"token-major operands take 2 .. 128 heads, got {h}")
+    if h % r != 0:
+        raise bad("the heads are no multiple of b_group")
+    hb = h // r
+    if bd == 4:
+        bS, b1, bh, b3 = b.shape
+        flags |= L.ASQ_BMM_B_TOKEN
+    else:
+        bS, b1, b3 = b.shape
+        bS, bh = (bS // hb, hb) if bS % hb == 0 else (-1, -1)
+    bK, N = (b1, b3) if kn else (b3, b1)
+    if bS != S or bh != hb or bK != K:
+        raise bad(f"shape mismatch: b must hold {S} sequences of {hb} heads with K = {K}")
+    if out_token:
+        flags |= L.ASQ_BMM_OUT_TOKEN
+    return flags | L.ASQ_BMM_HEADS(h), S * h, M, N, K, ((S, M, h, N) if out_token else (S * h, M, N))
+
+
+def bmm_i8(a, b, out_kind, alpha=1.0, b_group=1, out_token=False, heads=None):
     """Batched int8 A . B^T (reference bmm_s8t_s8n_{s32t,f32t,s8t}, csrc/kernels/bmm.cu:10-211): a int8 [B, M, K], b int8 [B, N, K] ->
     a new [B, M, N] tensor on the current stream.  out_kind: torch.int32 / L.ASQ_BMM_S32 (the exact accumulator; alpha ignored),
     torch.float32 / L.ASQ_BMM_F32 (alpha * float(acc)), torch.int8 / L.ASQ_BMM_S8 (sat_i8(rne(alpha * float(acc)))); alpha reaches the kernel as fp32.
     b_group = r > 1 (ASQ_BMM_B_GROUP, here and in the two ops below): b has B / r entries and a[i] meets b[i // r] -- the r query heads of a grouped-query
-    model on their shared K or V -- bit-identical to the call on b.repeat_interleave(r, 0) without the copy."""
-    return _bmm(a, b, alpha, out_kind, b_group=b_group)
+    model on their shared K or V -- bit-identical to the call on b.repeat_interleave(r, 0) without the copy.
+    Token-major operands (ASQ_BMM_*_TOKEN, here and in the two ops below), the layout of a q/k/v projection's output and of o_proj's input: a 4-D a is
+    [S, M, H, K], a 4-D b [S, N, H / r, K], and out_token=True returns [S, M, H, N]; each must be contiguous (a slice of a fused q|k|v buffer is made so by
+    the caller), H is 2 .. 128.  A 3-D operand next to them is dense over the S * H entries (sequence-major, b: S * H / r); heads=H states H when a is 3-D.
+    Bit-identical to the 3-D call on .permute(0, 2, 1, 3) copies, without the copies."""
+    return _bmm(a, b, alpha, out_kind, 0, b_group, out_token, heads)
 
 
-def bmm_i8_kn(a, b, out_kind, alpha=1.0, b_group=1):
+def bmm_i8_kn(a, b, out_kind, alpha=1.0, b_group=1, out_token=False, heads=None):
     """Batched int8 A . B with b row-major (asq_bmm_i8 with ASQ_BMM_B_KN): a int8 [B, M, K], b int8 [B, K, N] -> a new [B, M, N] tensor on the current
     stream, bit-identical to bmm_i8(a, b.transpose(1, 2).contiguous(), out_kind, alpha) without the copy.  out_kind: as bmm_i8 (a dtype or a plain
-    ASQ_BMM_S32 / _F32 / _S8 code); ASQ_BMM_B_KN may be set on a code and is implied."""
-    return _bmm(a, b, alpha, out_kind, L.ASQ_BMM_B_KN, b_group)
+    ASQ_BMM_S32 / _F32 / _S8 code); ASQ_BMM_B_KN may be set on a code and is implied.  Token-major: as bmm_i8, a 4-D b being [S, K, H / r, N] (V as its
+    projection or a KV cache holds it)."""
+    return _bmm(a, b, alpha, out_kind, L.ASQ_BMM_B_KN, b_group, out_token, heads)
 
 
-def bmm_i8_softmax_q8(a, b, alpha, causal=False, b_group=1):
+def bmm_i8_softmax_q8(a, b, alpha, causal=False, b_group=1, heads=None):
     """QK^T with the softmax -> int8 epilogue fused (asq_bmm_i8 with ASQ_BMM_S8 | ASQ_BMM_SOFTMAX [| ASQ_BMM_CAUSAL]): a int8 [B, M, K], b int8 [B, N, K]
     -> a new int8 [B, M, N] = rne(127 * softmax(alpha * (a . b^T), -1)) on the current stream, values 0 .. 127; the fp32 scores never reach memory.
-    causal: key n is visible to query m iff n <= m + (N - M); invisible elements are 0.  alpha reaches the kernel as fp32."""
-    return _bmm(a, b, alpha, L.ASQ_BMM_S8, L.ASQ_BMM_SOFTMAX | (L.ASQ_BMM_CAUSAL if causal else 0), b_group)
+    causal: key n is visible to query m iff n <= m + (N - M); invisible elements are 0.  alpha reaches the kernel as fp32.  Token-major a [S, M, H, K] and
+    b [S, N, H / r, K] as in bmm_i8; the result stays dense, [S * H, M, N], which is what P . V reads."""
+    return _bmm(a, b, alpha, L.ASQ_BMM_S8, L.ASQ_BMM_SOFTMAX | (L.ASQ_BMM_CAUSAL if causal else 0), b_group, False, heads)
 
 
 def bmm_kernel_name(batch, M, N, K, out_kind=L.ASQ_BMM_F32):

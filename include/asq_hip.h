@@ -406,7 +406,7 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
 #define ASQ_BMM_F32 1 /* bmm_s8t_s8n_f32t: out float = alpha * float(acc)            */
 #define ASQ_BMM_S8 2  /* bmm_s8t_s8n_s8t : out int8  = sat_i8(rne(alpha*float(acc))) */
 /* out_kind is a base kind in the low bits plus flags.  The valid values are 0, 1, 2, ASQ_BMM_S8 | ASQ_BMM_SOFTMAX (18) and
- * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50), and ASQ_BMM_B_KN | {0, 1, 2} (128, 129, 130), each optionally with ASQ_BMM_B_GROUP(r) (bits 16 .. 23, below); every other value is ASQ_ERR_DTYPE / "none".
+ * ASQ_BMM_S8 | ASQ_BMM_SOFTMAX | ASQ_BMM_CAUSAL (50), and ASQ_BMM_B_KN | {0, 1, 2} (128, 129, 130), each optionally with ASQ_BMM_B_GROUP(r) (bits 16 .. 23, below) and with the token-major flags (bits 9 .. 11 and 24 .. 30, below); every other value is ASQ_ERR_DTYPE / "none".
  *
  * The softmax kinds turn QK^T into the int8 probabilities that P.V consumes (asq_bmm_i8(p, vT, ASQ_BMM_S8) with alpha = v_scale / (127 * out_scale))
  * without the fp32 scores ever reaching memory.  out is int8 [batch, M, N]; per batch i and row m
@@ -438,9 +438,30 @@ int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, const uint8_t *
  * equals the base kind called on b repeated r times along the batch.  Everything else is the base kind's: the epilogues, any M, N, K >= 0, alignment
  * freedom, K = 0, the empty output, no workspace, determinism, the argument rules and their order.  One more error: batch % r != 0 is ASQ_ERR_DIM, reported
  * directly after a bad out_kind (so also when M or N is 0); asq_bmm_kernel_name answers "none" for it and otherwise the base kind's name -- these are the
- * same kernels.  A bit set in 9 .. 15 or in 24 and above stays ASQ_ERR_DTYPE / "none".  No version bump: probe with
+ * same kernels.  Bits 9 .. 11 and 24 .. 30 belong to the token-major flags below; any other bit stays ASQ_ERR_DTYPE / "none".  No version bump: probe with
  * asq_bmm_kernel_name(r, M, N, K, kind | ASQ_BMM_B_GROUP(r)) != "none"; an older library answers "none". */
 #define ASQ_BMM_B_GROUP(r) (((r) - 1) << 16)
+/* ASQ_BMM_A_TOKEN, ASQ_BMM_B_TOKEN, ASQ_BMM_OUT_TOKEN with ASQ_BMM_HEADS(h), h = 2 .. 128: token-major operands, the layout an attention's linears write and
+ * read ([B * S, H * d] = [B, S, H, d]), so no head permute surrounds the attention core.  h is the number of batch entries per sequence (the heads of a / out):
+ * entry i is head i % h of sequence i / h.  With ASQ_BMM_B_GROUP(r) b has hb = h / r heads and entry i uses b head (i % h) / r of its sequence -- the b entry
+ * i / r of the group flag.  A flagged operand is
+ *   ASQ_BMM_A_TOKEN    a   [batch / h, M, h, K]    row m of entry i starts at (((i / h) * M + m) * h + i % h) * K
+ *   ASQ_BMM_B_TOKEN    b   [batch / h, N, hb, K],  with ASQ_BMM_B_KN [batch / h, K, hb, N]
+ *   ASQ_BMM_OUT_TOKEN  out [batch / h, M, h, N]
+ * dense in that shape; an operand without its flag stays dense [entries, rows, cols].  Every output element equals, bit for bit, the same out_kind without
+ * these flags called on head-major copies of the flagged operands (out permuted back): the arithmetic, its order and the epilogues are the existing ones and
+ * only addresses differ.  Valid: any of the eight values above, optionally with ASQ_BMM_B_GROUP(r), plus a non-empty subset of the three flags AND a
+ * non-zero ASQ_BMM_HEADS field; ASQ_BMM_OUT_TOKEN is refused on the softmax kinds (P stays dense for P.V).  A flag with a zero field, a field without a flag,
+ * bit 8, bits 12 .. 15 and bit 31 stay ASQ_ERR_DTYPE / "none".  Two more errors: batch % h != 0 or h % r != 0 is ASQ_ERR_DIM, reported directly after the
+ * batch % r check (before the pointer checks, also on an empty problem; a batch of 2^57 entries or more, which no memory holds, is refused with them); asq_bmm_kernel_name answers "none" for them and otherwise the base kind's name --
+ * the same kernel forms.  Everything else is the base kind's: any M, N, K >= 0, alignment freedom (the unguarded load path is taken wherever the base kind
+ * takes it: the row pitches are multiples of 16 when K, or N for ASQ_BMM_B_KN, is), K = 0, the empty output, no workspace, determinism and batch
+ * independence.  No version bump: probe with asq_bmm_kernel_name(h, M, N, K, kind | ASQ_BMM_A_TOKEN | ASQ_BMM_HEADS(h)) != "none"; an older library
+ * answers "none". */
+#define ASQ_BMM_A_TOKEN 0x200
+#define ASQ_BMM_B_TOKEN 0x400
+#define ASQ_BMM_OUT_TOKEN 0x800
+#define ASQ_BMM_HEADS(h) (((h) - 1) << 24)
 int asq_bmm_i8(const int8_t *a, const int8_t *b, void *out, int out_kind,
                int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, void *stream);
 const char *asq_bmm_kernel_name(int64_t batch, int64_t M, int64_t N, int64_t K, int out_kind);
