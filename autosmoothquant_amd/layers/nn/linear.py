@@ -13,6 +13,7 @@ Checkpoint contract (what ``state_dict`` holds; reference :49-66, :138-149, :253
 Scalar scales live on the HOST after any ``.cuda()/.half()/.to()`` (reference ``_apply``
 :68-72), so reading them never synchronises the device.
 """
+import collections
 import threading
 
 import torch
@@ -108,20 +109,20 @@ class _W8A8Base(torch.nn.Module):
         skips the re-derivation and the re-validation: empty + one C-ABI call.  Anything else returns None and takes the full path, which refreshes the record.
         Not used for shapes that run on offset images (their image follows the weight's version; those forwards are GPU-bound anyway)."""
         fc = self.__dict__.get("_fast_state")
-        if fc is None or x.shape != fc[0] or x.dtype is not fc[1] or not x.is_cuda or x.get_device() != fc[2] or not x.is_contiguous():
+        if fc is None or x.shape != fc.x_shape or x.dtype is not fc.dtype or not x.is_cuda or x.get_device() != fc.dev_index or not x.is_contiguous():
             return None
         b = self._buffers
-        if b["weight"] is not fc[3] or b.get("bias") is not fc[4] or _cur_dev() != fc[2]:
+        if b["weight"] is not fc.weight or b.get("bias") is not fc.bias or _cur_dev() != fc.dev_index:
             return None
-        for name, t, ver in fc[5]:
+        for name, t, ver in fc.scalars:
             u = b[name]
             if u is not t or u._version != ver:
                 return None
-        out = torch.empty(fc[6], dtype=fc[1], device=fc[7])
+        out = torch.empty(fc.out_shape, dtype=fc.dtype, device=fc.device)
         stream = ops._stream(x)
-        ws, nbytes = ops._forward_ws(fc[8], fc[9], fc[10], fc[11], fc[7], stream)
-        rc = fc[12](x.data_ptr(), fc[13], fc[3].data_ptr(), out.data_ptr(), fc[9], fc[10], fc[11], fc[14], fc[15], fc[16], None, None if fc[4] is None else fc[4].data_ptr(),
-                    None if ws is None else ws.data_ptr(), nbytes, stream)
+        ws, nbytes = ops._forward_ws(fc.lib, fc.M, fc.N, fc.K, fc.device, stream)
+        rc = fc.entry(x.data_ptr(), fc.dt_code, fc.weight.data_ptr(), out.data_ptr(), fc.M, fc.N, fc.K, fc.act_code, fc.quant_scale, fc.s_scalar, None,
+                      None if fc.bias is None else fc.bias.data_ptr(), None if ws is None else ws.data_ptr(), nbytes, stream)
         if rc:
             ops.L.check(rc, "asq_linear_w8a8_forward")
         return out
@@ -314,6 +315,10 @@ def _prequantized_forward(mod, qa, s_scalar, s_col):
     return out.view(*qa.lead, mod.out_features)
 
 
+# What _W8A8Base._fast replays: the input geometry it holds for, the module's state tensors it was derived from, and the derived asq_linear_w8a8_forward call
+_FastState = collections.namedtuple("_FastState", "x_shape dtype dev_index weight bias scalars out_shape device lib M N K entry dt_code act_code quant_scale s_scalar")
+
+
 def _module_forward(mod, x, mode, qs, s_scalar, s_col):
     """quantise -> GEMM + epilogue for a floating input: every forward quantises its own input, as the reference does
     (layers/nn/linear.py:88-96).  Callers that KNOW several modules read one tensor (q/k/v, gate/up) quantise it once,
@@ -344,8 +349,10 @@ def _module_forward(mod, x, mode, qs, s_scalar, s_col):
         try:
             scal = tuple((n, mod._buffers[n], mod._buffers[n]._version) for n in mod._host_scalars)
             lib = ops.L.lib()
-            mod.__dict__["_fast_state"] = (x.shape, x.dtype, x.get_device(), w, bias, scal, (*lead, mod.out_features), x.device, lib, x2.shape[0], mod.out_features, mod.in_features,
-                                           lib.asq_linear_w8a8_forward, ops._DT[x.dtype], _ACT_CODE[mode], float(qs), float(s_scalar))
+            mod.__dict__["_fast_state"] = _FastState(
+                x_shape=x.shape, dtype=x.dtype, dev_index=x.get_device(), weight=w, bias=bias, scalars=scal, out_shape=(*lead, mod.out_features), device=x.device, lib=lib,
+                M=x2.shape[0], N=mod.out_features, K=mod.in_features, entry=lib.asq_linear_w8a8_forward, dt_code=ops._DT[x.dtype], act_code=_ACT_CODE[mode],
+                quant_scale=float(qs), s_scalar=float(s_scalar))
         except RuntimeError:   # (inference tensors have no version counter: no cached call)
             mod.__dict__.pop("_fast_state", None)
     else:

@@ -2,9 +2,8 @@
 
 Every function validates dtype / device / contiguity / shape and raises instead of
 falling back: the reference passes raw ``data_ptr`` with no checks (bindings.cpp:73-80)."""
-import threading
-
 import os
+import threading
 
 import torch
 
@@ -157,49 +156,141 @@ def _same_device(*ts):
     return d
 
 
-def gemm_i8_i32(x, w, out):
-    """out[M,N] i32 = x[M,K] i8 . w[N,K]^T i8  (K1, bindings.cpp:69-84)."""
+def _operand(t, name, dtype=None, numel=None, shape=None, optional=False):
+    """A tensor whose pointer goes to the C-ABI: a contiguous HIP tensor (_dev), then of `dtype` with `numel` elements or of `shape` -- "s_col must be float32
+    with 4096 elements", "row_off must be int32 with 64 elements".  optional: None passes."""
+    if t is None and optional:
+        return None
+    _dev(t, name)
+    if (dtype is not None and t.dtype != dtype) or (numel is not None and t.numel() != numel) or (shape is not None and tuple(t.shape) != shape):
+        what = f"with {numel} elements" if shape is None else f"of shape {list(shape)}"
+        raise ValueError(f"{name} must be {str(t.dtype if dtype is None else dtype)[6:]} {what}, got {t.dtype} {list(t.shape)}")
+    return t
+
+
+def _pair(x, w, dtype, xname="xq", wname="weight", stack=False, even=False):
+    """Activation x [M,K] and weight w [N,K] (stack: [G,N,K]) of `dtype` with equal K (even: N = 2 F, a gate || up operand) -> (M, N, K), stack: (M, N, K, G)."""
+    _dev(x, xname), _dev(w, wname)
+    if x.dtype != dtype or w.dtype != dtype or x.dim() != 2 or w.dim() != (3 if stack else 2) or x.shape[1] != w.shape[-1] or (even and w.shape[-2] % 2):
+        raise ValueError(f"{xname} [M,K] and {wname} [{'G,' if stack else ''}{'2F' if even else 'N'},K] must be {str(dtype)[6:]} with equal K, "
+                         f"got {x.dtype} {list(x.shape)} and {w.dtype} {list(w.shape)}")
+    return (x.shape[0], w.shape[1], x.shape[1], w.shape[0]) if stack else (x.shape[0], w.shape[0], x.shape[1])
+
+
+def _offsets(row_off, col_off, M, ncol, optional=False):
+    """The offset operand images' row_off int32 [M,2] and col_off int32 [ncol,2] (by length: col_off of a stack is [G,N,2]); optional: both or neither."""
+    if optional and (row_off is None or col_off is None):
+        if row_off is not col_off:
+            raise ValueError("row_off and col_off come together")
+        return
+    _operand(row_off, "row_off", torch.int32, 2 * M), _operand(col_off, "col_off", torch.int32, 2 * ncol)
+
+
+def _out(out, shape, dtype, device):
+    """The `out=` argument of an op: a new tensor when absent, otherwise checked (contiguous, `dtype`, `shape`, on `device`) and its version counter bumped."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if device.type == "cuda":
+        _dev(out, "out")
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"out has wrong dtype/shape: it must be a contiguous {str(dtype)[6:]} {list(shape)} tensor on {device}, got {out.dtype} {list(out.shape)} on {out.device}")
+    _bump_version(out)
+    return out
+
+
+def _bump_version(t):
+    """A raw C-ABI write into a caller-provided tensor is made visible to torch's version counter (autograd's saved-tensor checks and
+    any caller that keys on ._version).  Inference tensors have no counter: nothing to do."""
+    try:
+        torch.autograd.graph.increment_version(t)
+    except Exception:
+        pass
+
+
+def _rows_out(M, K, dev, per_token, offsets):
+    """What a row quantiser writes: (xq int8 [M,K], s_row f32 [M] or None, row_off int32 [M,2] or None)."""
+    return (torch.empty((M, K), dtype=torch.int8, device=dev), torch.empty((M,), dtype=torch.float32, device=dev) if per_token else None,
+            torch.empty((M, 2), dtype=torch.int32, device=dev) if offsets else None)
+
+
+def _call(name, *args):
+    """The C-ABI entry `name` on the current device; a non-zero code raises under that same name (_lib.check)."""
+    rc = getattr(L.lib(), name)(*args)
+    if rc:
+        L.check(rc, name)
+
+
+def _launch(name, dev, *args):
+    """_call with `dev` made the current device (the C-ABI launches on the current device)."""
+    with _on(dev):
+        _call(name, *args)
+
+
+SILU_EXACT_DEFAULT = os.environ.get("ASQ_SILU_EXACT", "0") == "1"   # the bit-reproducible SiLU everywhere `fast` is left to the default
+
+
+def _silu_flag(fast):
+    """ASQ_SILU_FAST or 0 for an op's `fast` argument; None is the process default (fast, unless ASQ_SILU_EXACT=1)."""
+    return L.ASQ_SILU_FAST if (not SILU_EXACT_DEFAULT if fast is None else fast) else 0
+
+
+def _epi_order(order):
+    return L.ASQ_EPI_SCALE_FIRST if order == "scale_first" else L.ASQ_EPI_ACC_FIRST
+
+
+def _gemm_out_check(x, w, out, out_dtype, what):
+    """operands of the two plain GEMMs (reference-named: a wrong dtype is a RuntimeError) -> (M, N, K, device)"""
     _dev(x, "input"), _dev(w, "weight"), _dev(out, "out")
-    if x.dtype != torch.int8 or w.dtype != torch.int8 or out.dtype != torch.int32:
-        raise RuntimeError("expected int8 input, int8 weight, int32 out")
+    if x.dtype != torch.int8 or w.dtype != torch.int8 or out.dtype != out_dtype:
+        raise RuntimeError(what)
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or tuple(out.shape) != (x.shape[0], w.shape[0]):
         raise ValueError(f"shape mismatch: input {tuple(x.shape)}, weight {tuple(w.shape)}, out {tuple(out.shape)}")
-    dev = _same_device(x, w, out)
+    return x.shape[0], w.shape[0], x.shape[1], _same_device(x, w, out)
+
+
+def gemm_i8_i32(x, w, out):
+    """out[M,N] i32 = x[M,K] i8 . w[N,K]^T i8  (K1, bindings.cpp:69-84)."""
+    M, N, K, dev = _gemm_out_check(x, w, out, torch.int32, "expected int8 input, int8 weight, int32 out")
     with _on(dev):
-        ws, n = _gemm_ws(x.shape[0], w.shape[0], x.shape[1], dev, _stream(x))
-        L.check(L.lib().asq_gemm_i8_i32(x.data_ptr(), w.data_ptr(), out.data_ptr(), x.shape[0], w.shape[0], x.shape[1], _ptr(ws), n,
-                                        _stream(x)), "asq_gemm_i8_i32")
+        st = _stream(x)
+        ws, n = _gemm_ws(M, N, K, dev, st)
+        _call("asq_gemm_i8_i32", x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, _ptr(ws), n, st)
     return out
 
 
 def gemm_i8_i8(x, w, out, alpha, beta=0.0):
     """out[M,N] i8 = sat(rne(alpha*acc + beta*out))  (K3-K5, bindings.cpp:86-142)."""
-    _dev(x, "input"), _dev(w, "weight"), _dev(out, "out")
-    if x.dtype != torch.int8 or w.dtype != torch.int8 or out.dtype != torch.int8:
-        raise RuntimeError("expected int8 input, weight and out")
-    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or tuple(out.shape) != (x.shape[0], w.shape[0]):
-        raise ValueError(f"shape mismatch: input {tuple(x.shape)}, weight {tuple(w.shape)}, out {tuple(out.shape)}")
-    dev = _same_device(x, w, out)
+    M, N, K, dev = _gemm_out_check(x, w, out, torch.int8, "expected int8 input, weight and out")
     with _on(dev):
-        ws, n = _gemm_ws(x.shape[0], w.shape[0], x.shape[1], dev, _stream(x))
-        L.check(L.lib().asq_gemm_i8_i8(x.data_ptr(), w.data_ptr(), out.data_ptr(), x.shape[0], w.shape[0], x.shape[1],
-                                       float(alpha), float(beta), _ptr(ws), n, _stream(x)), "asq_gemm_i8_i8")
+        st = _stream(x)
+        ws, n = _gemm_ws(M, N, K, dev, st)
+        _call("asq_gemm_i8_i8", x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K, float(alpha), float(beta), _ptr(ws), n, st)
     return out
+
+
+def _float_rows(x):
+    """a row op's input: x [M,K] f32/f16/bf16 on a HIP device -> (M, K)"""
+    _dev(x, "x")
+    if x.dtype not in _DT or x.dim() != 2:
+        raise ValueError("x must be a 2-D float32/float16/bfloat16 tensor")
+    return x.shape
+
+
+def _quantize_act(x, mode, quant_scale, offsets):
+    M, K = _float_rows(x)
+    xq, s_row, row_off = _rows_out(M, K, x.device, mode == "per-token", offsets)
+    head = (x.data_ptr(), _DT[x.dtype], _ACT[mode], float(quant_scale), xq.data_ptr(), _ptr(s_row))
+    if offsets:
+        _launch("asq_quantize_act_off", x.device, *head, row_off.data_ptr(), M, K, _stream(x))
+        return xq, s_row, row_off
+    _launch("asq_quantize_act", x.device, *head, M, K, _stream(x))
+    return xq, s_row
 
 
 def quantize_act(x, mode, quant_scale=1.0):
     """x [M,K] f32/f16/bf16 -> (xq int8 [M,K], s_row f32 [M] or None).  mode in
     {"per-token", "per-tensor-round", "per-tensor-div"} (linear.py:88-96, 283-292)."""
-    _dev(x, "x")
-    if x.dtype not in _DT or x.dim() != 2:
-        raise ValueError("x must be a 2-D float32/float16/bfloat16 tensor")
-    M, K = x.shape
-    xq = torch.empty((M, K), dtype=torch.int8, device=x.device)
-    s_row = torch.empty((M,), dtype=torch.float32, device=x.device) if mode == "per-token" else None
-    with _on(x.device):
-        L.check(L.lib().asq_quantize_act(x.data_ptr(), _DT[x.dtype], _ACT[mode], float(quant_scale), xq.data_ptr(), _ptr(s_row),
-                                         M, K, _stream(x)), "asq_quantize_act")
-    return xq, s_row
+    return _quantize_act(x, mode, quant_scale, False)
 
 
 def offsets_supported(M, N, K, out_dtype):
@@ -212,26 +303,25 @@ def forward_is_fused(M, N, K, dtype, mode="per-tensor-round"):
     return dtype in _DT and bool(L.lib().asq_forward_fused_supported(int(M), int(N), int(K), _DT[dtype], _ACT[mode]))
 
 
-def linear_w8a8_forward_fused(x2d, w, act_mode, quant_scale, s_scalar, s_col=None, bias=None):
-    """linear_w8a8_forward as ONE launch, on request (asq_linear_w8a8_forward_fused): any shape the fused kernel can run (<= 16 rows, K % 128 == 0, the int8 activation
-    image fits 64 KiB of LDS), also where linear_w8a8_forward itself would take two launches.  Raises on shapes outside the kernel's limits."""
+def _forward_operands(x2d, w, s_col, bias):
+    """operands of the whole-forward entries: x [M,K] float, weight int8 [N,K], s_col / bias f32 [N] or None -> (M, N, K, device)"""
     _dev(x2d, "x"), _dev(w, "weight")
     if x2d.dtype not in _DT:
         raise ValueError(f"unsupported activation dtype {x2d.dtype}")
-    if w.dtype != torch.int8 or x2d.dim() != 2 or w.dim() != 2 or x2d.shape[1] != w.shape[1] or not x2d.is_contiguous() or not w.is_contiguous():
-        raise ValueError(f"shape/dtype mismatch: x {tuple(x2d.shape)} {x2d.dtype}, weight {tuple(w.shape)} {w.dtype} (both contiguous)")
-    M, K = x2d.shape
+    if w.dtype != torch.int8 or x2d.dim() != 2 or w.dim() != 2 or x2d.shape[1] != w.shape[1]:
+        raise ValueError(f"shape/dtype mismatch: x {tuple(x2d.shape)} {x2d.dtype}, weight {tuple(w.shape)} {w.dtype}")
     N = w.shape[0]
-    for name, t in (("s_col", s_col), ("bias", bias)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != N:
-                raise ValueError(f"{name} must be float32 with {N} elements")
-    dev = _same_device(x2d, w, s_col, bias)
+    _operand(s_col, "s_col", torch.float32, N, optional=True), _operand(bias, "bias", torch.float32, N, optional=True)
+    return x2d.shape[0], N, x2d.shape[1], _same_device(x2d, w, s_col, bias)
+
+
+def linear_w8a8_forward_fused(x2d, w, act_mode, quant_scale, s_scalar, s_col=None, bias=None):
+    """linear_w8a8_forward as ONE launch, on request (asq_linear_w8a8_forward_fused): any shape the fused kernel can run (<= 16 rows, K % 128 == 0, the int8 activation
+    image fits 64 KiB of LDS), also where linear_w8a8_forward itself would take two launches.  Raises on shapes outside the kernel's limits."""
+    M, N, K, dev = _forward_operands(x2d, w, s_col, bias)
     out = torch.empty((M, N), dtype=x2d.dtype, device=dev)
-    with _on(dev):
-        L.check(L.lib().asq_linear_w8a8_forward_fused(x2d.data_ptr(), _DT[x2d.dtype], w.data_ptr(), out.data_ptr(), M, N, K, _ACT[act_mode], float(quant_scale), float(s_scalar),
-                                                      _ptr(s_col), _ptr(bias), _stream(x2d)), "asq_linear_w8a8_forward_fused")
+    _launch("asq_linear_w8a8_forward_fused", dev, x2d.data_ptr(), _DT[x2d.dtype], w.data_ptr(), out.data_ptr(), M, N, K, _ACT[act_mode], float(quant_scale), float(s_scalar),
+            _ptr(s_col), _ptr(bias), _stream(x2d))
     return out
 
 
@@ -259,61 +349,32 @@ def interleave_gate_up(w_gate, w_up, out=None, block=None):
     return out
 
 
+def _gate_up(xq, w_gu, out_dtype, code_dtype, s_gate, s_up, s_row, fast, row_off, col_off, out, quant_scale=None):
+    """linear_w8a8_gate_up (quant_scale None: out in out_dtype = code_dtype) and linear_w8a8_gate_up_q8 (int8 out, the epilogue's arithmetic in code_dtype)"""
+    M, N, K = _pair(xq, w_gu, torch.int8, "xq", "w_gu", even=True)
+    F_ = N // 2
+    _operand(s_row, "s_row", torch.float32, M, optional=True)
+    _offsets(row_off, col_off, M, N, optional=True)
+    out = _out(out, (M, F_), out_dtype, xq.device)
+    dev = _same_device(xq, w_gu, out, s_row, row_off, col_off)
+    head = (xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[code_dtype], M, F_, K, float(s_gate), float(s_up), _ptr(s_row), _silu_flag(fast))
+    if quant_scale is None:
+        _launch("asq_linear_w8a8_gate_up", dev, *head, _ptr(row_off), _ptr(col_off), _stream(xq))
+    else:
+        _launch("asq_linear_w8a8_gate_up_q8", dev, *head, float(quant_scale), _ptr(row_off), _ptr(col_off), _stream(xq))
+    return out
+
+
 def linear_w8a8_gate_up(xq, w_gu, out_dtype, s_gate, s_up, s_row=None, fast=None, row_off=None, col_off=None, out=None):
     """SiLU(gate(x)) * up(x) in ONE GEMM over the interleaved weight (asq_linear_w8a8_gate_up): out [M, F] in out_dtype, bit-identical to
     linear_w8a8 (gate), linear_w8a8 (up) and the SiLU * up of silu_mul_quantize(fast=...).  row_off / col_off: offset operand images of xq and w_gu."""
-    _dev(xq, "xq"), _dev(w_gu, "w_gu")
-    if xq.dtype != torch.int8 or w_gu.dtype != torch.int8 or xq.dim() != 2 or w_gu.dim() != 2 or xq.shape[1] != w_gu.shape[1] or w_gu.shape[0] % 2:
-        raise ValueError("xq [M,K] and w_gu [2F,K] must be int8 with equal K")
-    if not (xq.is_contiguous() and w_gu.is_contiguous()):
-        raise ValueError("xq / w_gu must be contiguous")
-    M, K = xq.shape
-    F_ = w_gu.shape[0] // 2
-    if s_row is not None:
-        _dev(s_row, "s_row")
-        if s_row.dtype != torch.float32 or s_row.numel() != M:
-            raise ValueError(f"s_row must be float32 with {M} elements")
-    if (row_off is None) != (col_off is None):
-        raise ValueError("row_off and col_off come together")
-    if row_off is not None and (row_off.dtype != torch.int32 or row_off.numel() != 2 * M or col_off.dtype != torch.int32 or col_off.numel() != 4 * F_):
-        raise ValueError("row_off must be int32 [M,2] and col_off int32 [2F,2]")
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
-    if out is None:
-        out = torch.empty((M, F_), dtype=out_dtype, device=xq.device)
-    dev = _same_device(xq, w_gu, out, s_row, row_off, col_off)
-    with _on(dev):
-        L.check(L.lib().asq_linear_w8a8_gate_up(xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[out_dtype], M, F_, K, float(s_gate), float(s_up), _ptr(s_row),
-                                                L.ASQ_SILU_FAST if fast else 0, _ptr(row_off), _ptr(col_off), _stream(xq)), "asq_linear_w8a8_gate_up")
-    return out
+    return _gate_up(xq, w_gu, out_dtype, out_dtype, s_gate, s_up, s_row, fast, row_off, col_off, out)
 
 
 def linear_w8a8_gate_up_q8(xq, w_gu, act_dtype, s_gate, s_up, quant_scale, s_row=None, fast=None, row_off=None, col_off=None):
     """linear_w8a8_gate_up with the consumer's per-tensor quantiser as part of the epilogue (asq_linear_w8a8_gate_up_q8): int8 [M, F] =
     quantize_act(linear_w8a8_gate_up(..., act_dtype), "per-tensor-div", quant_scale)[0], bit for bit; the fp tensor never exists."""
-    _dev(xq, "xq"), _dev(w_gu, "w_gu")
-    if xq.dtype != torch.int8 or w_gu.dtype != torch.int8 or xq.dim() != 2 or w_gu.dim() != 2 or xq.shape[1] != w_gu.shape[1] or w_gu.shape[0] % 2:
-        raise ValueError("xq [M,K] and w_gu [2F,K] must be int8 with equal K")
-    if not (xq.is_contiguous() and w_gu.is_contiguous()):
-        raise ValueError("xq / w_gu must be contiguous")
-    M, K = xq.shape
-    F_ = w_gu.shape[0] // 2
-    if s_row is not None:
-        _dev(s_row, "s_row")
-        if s_row.dtype != torch.float32 or s_row.numel() != M:
-            raise ValueError(f"s_row must be float32 with {M} elements")
-    if (row_off is None) != (col_off is None):
-        raise ValueError("row_off and col_off come together")
-    if row_off is not None and (row_off.dtype != torch.int32 or row_off.numel() != 2 * M or col_off.dtype != torch.int32 or col_off.numel() != 4 * F_):
-        raise ValueError("row_off must be int32 [M,2] and col_off int32 [2F,2]")
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
-    out = torch.empty((M, F_), dtype=torch.int8, device=xq.device)
-    dev = _same_device(xq, w_gu, out, s_row, row_off, col_off)
-    with _on(dev):
-        L.check(L.lib().asq_linear_w8a8_gate_up_q8(xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[act_dtype], M, F_, K, float(s_gate), float(s_up), _ptr(s_row),
-                                                   L.ASQ_SILU_FAST if fast else 0, float(quant_scale), _ptr(row_off), _ptr(col_off), _stream(xq)), "asq_linear_w8a8_gate_up_q8")
-    return out
+    return _gate_up(xq, w_gu, torch.int8, act_dtype, s_gate, s_up, s_row, fast, row_off, col_off, None, quant_scale)
 
 
 def grouped_gate_up_supported(M, F_, K, out_dtype):
@@ -326,10 +387,7 @@ def interleave_gate_up_stack(w1, w3, out=None):
     if w1.shape != w3.shape or w1.dim() != 3:
         raise ValueError("w1 / w3 must be [G, F, K] stacks of one shape")
     G, F_, K = w1.shape
-    if out is None:
-        out = torch.empty((G, 2 * F_, K), dtype=w1.dtype, device=w1.device)
-    elif tuple(out.shape) != (G, 2 * F_, K) or out.dtype != w1.dtype or out.device != w1.device or not out.is_contiguous():
-        raise ValueError("out must be a contiguous [G, 2F, K] buffer of the stacks' dtype on their device")
+    out = _out(out, (G, 2 * F_, K), w1.dtype, w1.device)
     for g in range(G):
         interleave_gate_up(w1[g], w3[g], out=out[g])
     return out
@@ -339,31 +397,17 @@ def linear_w8a8_grouped_gate_up(xq, w_gu, group_offsets, s_gate, s_up, out_dtype
     """SiLU(w1 x) * (w3 x) of ALL groups in ONE grouped launch over the interleaved stacks w_gu [G, 2F, K] (asq_linear_w8a8_grouped_gate_up; reference
     models/mixtral.py:99-101,142-145): out [M, F], bit-identical to linear_w8a8_grouped (w1), (w3) and the SiLU * up of silu_mul_quantize(fast=...).  Per-tensor
     activations.  row_off / col_off: offset operand images of xq and of the stack viewed as [G * 2F, K]."""
-    _dev(xq, "xq"), _dev(w_gu, "w_gu"), _dev(group_offsets, "group_offsets"), _dev(s_gate, "s_gate"), _dev(s_up, "s_up")
-    if xq.dtype != torch.int8 or w_gu.dtype != torch.int8 or xq.dim() != 2 or w_gu.dim() != 3 or xq.shape[1] != w_gu.shape[2] or w_gu.shape[1] % 2:
-        raise ValueError("xq [M,K] int8 and w_gu [G,2F,K] int8 with equal K expected")
-    if not (xq.is_contiguous() and w_gu.is_contiguous()):
-        raise ValueError("xq / w_gu must be contiguous")
-    M, K = xq.shape
-    G, F_ = w_gu.shape[0], w_gu.shape[1] // 2
-    if group_offsets.dtype != torch.int32 or group_offsets.numel() != G + 1:
-        raise ValueError("group_offsets must be int32 [G+1]")
-    for name, t in (("s_gate", s_gate), ("s_up", s_up)):
-        if t.dtype != torch.float32 or t.numel() != G:
-            raise ValueError(f"{name} must be float32 [G]")
-    if (row_off is None) != (col_off is None):
-        raise ValueError("row_off and col_off come together")
-    if row_off is not None and (row_off.dtype != torch.int32 or row_off.numel() != 2 * M or col_off.dtype != torch.int32 or col_off.numel() != 4 * G * F_):
-        raise ValueError("row_off must be int32 [M,2] and col_off int32 [G,2F,2]")
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
+    M, N, K, G = _pair(xq, w_gu, torch.int8, "xq", "w_gu", stack=True, even=True)
+    F_ = N // 2
+    _operand(group_offsets, "group_offsets", torch.int32, G + 1), _operand(s_gate, "s_gate", torch.float32, G), _operand(s_up, "s_up", torch.float32, G)
+    _offsets(row_off, col_off, M, G * N, optional=True)
     out = torch.empty((M, F_), dtype=out_dtype, device=xq.device)
     dev = _same_device(xq, w_gu, group_offsets, s_gate, s_up, row_off, col_off)
     with _on(dev):
-        lib, st = L.lib(), _stream(xq)
-        ws, n = _grouped_ws(lib, M, 2 * F_, K, G, dev, st)
-        L.check(lib.asq_linear_w8a8_grouped_gate_up(xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, F_, K, s_gate.data_ptr(),
-                                                    s_up.data_ptr(), L.ASQ_SILU_FAST if fast else 0, _ptr(row_off), _ptr(col_off), _ptr(ws), n, st), "asq_linear_w8a8_grouped_gate_up")
+        st = _stream(xq)
+        ws, n = _grouped_ws(L.lib(), M, N, K, G, dev, st)
+        _call("asq_linear_w8a8_grouped_gate_up", xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, F_, K, s_gate.data_ptr(),
+              s_up.data_ptr(), _silu_flag(fast), _ptr(row_off), _ptr(col_off), _ptr(ws), n, st)
     return out
 
 
@@ -389,74 +433,39 @@ def weight_offset_image(w, out=None):
     else:
         w_off = torch.empty_like(w)
         col_off = torch.empty((N, 2), dtype=torch.int32, device=w.device)
-    with _on(w.device):
-        L.check(L.lib().asq_weight_offset_image(w.data_ptr(), N, K, w_off.data_ptr(), col_off.data_ptr(), _stream(w)), "asq_weight_offset_image")
+    _launch("asq_weight_offset_image", w.device, w.data_ptr(), N, K, w_off.data_ptr(), col_off.data_ptr(), _stream(w))
     return w_off, col_off
 
 
 def quantize_act_off(x, mode, quant_scale=1.0):
     """quantize_act emitting the offset image: (xq' int8 [M,K], s_row f32 [M] or None, row_off int32 [M,2] = {cx[m], sum_k xq'[m,k]});
     xq' - cx[:, None] is exactly quantize_act's xq."""
-    _dev(x, "x")
-    if x.dtype not in _DT or x.dim() != 2:
-        raise ValueError("x must be a 2-D float32/float16/bfloat16 tensor")
-    M, K = x.shape
-    xq = torch.empty((M, K), dtype=torch.int8, device=x.device)
-    s_row = torch.empty((M,), dtype=torch.float32, device=x.device) if mode == "per-token" else None
-    row_off = torch.empty((M, 2), dtype=torch.int32, device=x.device)
-    with _on(x.device):
-        L.check(L.lib().asq_quantize_act_off(x.data_ptr(), _DT[x.dtype], _ACT[mode], float(quant_scale), xq.data_ptr(), _ptr(s_row), row_off.data_ptr(),
-                                             M, K, _stream(x)), "asq_quantize_act_off")
-    return xq, s_row, row_off
+    return _quantize_act(x, mode, quant_scale, True)
+
+
+def _vectors(s_row, s_col, bias, M, N):
+    """the optional f32 vectors of a linear's epilogue: s_row [M], s_col [N], bias [N]"""
+    _operand(s_row, "s_row", torch.float32, M, optional=True), _operand(s_col, "s_col", torch.float32, N, optional=True), _operand(bias, "bias", torch.float32, N, optional=True)
 
 
 def linear_w8a8_off(xq_off, w_off, row_off, col_off, out_dtype, s_scalar=1.0, s_row=None, s_col=None, bias=None, order="scale_first", out=None, out_split=0):
     """linear_w8a8 on offset operand images: bit-identical to linear_w8a8 on the plain operands (asq_linear_w8a8_off).
     out_split = n (2 .. 4, ASQ_EPI_OUT_SPLIT): the N weight rows are n stacked linears of N / n outputs each and the result is [n, M, N / n] -- out[s] is the
     dense [M, N / n] output of a call on rows s * N / n .. of w_off / col_off / s_col / bias; (N / n) % 256 == 0."""
-    _dev(xq_off, "xq"), _dev(w_off, "weight"), _dev(row_off, "row_off"), _dev(col_off, "col_off")
-    if xq_off.dtype != torch.int8 or w_off.dtype != torch.int8 or xq_off.dim() != 2 or w_off.dim() != 2 or xq_off.shape[1] != w_off.shape[1]:
-        raise ValueError("xq [M,K] and weight [N,K] must be int8 with equal K")
-    M, K = xq_off.shape
-    N = w_off.shape[0]
-    if row_off.dtype != torch.int32 or row_off.numel() != 2 * M or col_off.dtype != torch.int32 or col_off.numel() != 2 * N:
-        raise ValueError("row_off must be int32 [M,2] and col_off int32 [N,2]")
-    for name, t, n in (("s_row", s_row, M), ("s_col", s_col, N), ("bias", bias, N)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != n:
-                raise ValueError(f"{name} must be float32 with {n} elements")
+    M, N, K = _pair(xq_off, w_off, torch.int8)
+    _offsets(row_off, col_off, M, N)
+    _vectors(s_row, s_col, bias, M, N)
     if out_split and (out_split < 2 or N % out_split != 0):
         raise ValueError(f"out_split={out_split} must be 2 .. 4 and divide N={N}")
-    shape = (out_split, M, N // out_split) if out_split else (M, N)
-    if out is None:
-        out = torch.empty(shape, dtype=out_dtype, device=xq_off.device)
-    else:
-        _dev(out, "out")
-        if out.dtype != out_dtype or tuple(out.shape) != shape:
-            raise ValueError("out has wrong dtype/shape")
-        _bump_version(out)
+    out = _out(out, (out_split, M, N // out_split) if out_split else (M, N), out_dtype, xq_off.device)
     dev = _same_device(xq_off, w_off, out, row_off, col_off, s_row, s_col, bias)
-    flags = (L.ASQ_EPI_SCALE_FIRST if order == "scale_first" else L.ASQ_EPI_ACC_FIRST) | (L.ASQ_EPI_OUT_SPLIT(out_split) if out_split else 0)
-    with _on(dev):
-        L.check(L.lib().asq_linear_w8a8_off(xq_off.data_ptr(), w_off.data_ptr(), out.data_ptr(), _DT[out_dtype], M, N, K, float(s_scalar),
-                                            _ptr(s_row), _ptr(s_col), _ptr(bias), flags, row_off.data_ptr(), col_off.data_ptr(), _stream(xq_off)), "asq_linear_w8a8_off")
+    _launch("asq_linear_w8a8_off", dev, xq_off.data_ptr(), w_off.data_ptr(), out.data_ptr(), _DT[out_dtype], M, N, K, float(s_scalar), _ptr(s_row), _ptr(s_col), _ptr(bias),
+            _epi_order(order) | (L.ASQ_EPI_OUT_SPLIT(out_split) if out_split else 0), row_off.data_ptr(), col_off.data_ptr(), _stream(xq_off))
     return out
 
 
-def _bump_version(t):
-    """A raw C-ABI write into a caller-provided tensor is made visible to torch's version counter (autograd's saved-tensor checks and
-    any caller that keys on ._version).  Inference tensors have no counter: nothing to do."""
-    try:
-        torch.autograd.graph.increment_version(t)
-    except Exception:
-        pass
-
-
-def norm_quantize(x, weight, bias=None, eps=1e-5, per_token=False, offsets=False):
-    """Fused (scale-folded) RMSNorm / LayerNorm -> int8 activation (SURVEY 8f N1).  x [M,K]; weight (and bias for
-    LayerNorm) [K] in x's dtype.  Returns (xq int8 [M,K], s_row f32 [M] or None); offsets=True emits the offset image
-    (asq_norm_quantize_off) and returns (xq', s_row, row_off int32 [M,2])."""
+def _norm_operands(x, weight, bias):
+    """x [M,K] float, weight (and bias, or None) [K] of x's dtype -> (M, K)"""
     _dev(x, "x"), _dev(weight, "weight")
     if x.dtype not in _DT or x.dim() != 2 or weight.dtype != x.dtype or weight.numel() != x.shape[1]:
         raise ValueError("x must be 2-D float and weight a [K] tensor of the same dtype")
@@ -464,53 +473,48 @@ def norm_quantize(x, weight, bias=None, eps=1e-5, per_token=False, offsets=False
         _dev(bias, "bias")
         if bias.dtype != x.dtype or bias.numel() != x.shape[1]:
             raise ValueError("bias must match weight")
-    M, K = x.shape
-    xq = torch.empty((M, K), dtype=torch.int8, device=x.device)
-    s_row = torch.empty((M,), dtype=torch.float32, device=x.device) if per_token else None
-    row_off = torch.empty((M, 2), dtype=torch.int32, device=x.device) if offsets else None
-    with _on(x.device):
-        if offsets:
-            L.check(L.lib().asq_norm_quantize_off(x.data_ptr(), _DT[x.dtype], weight.data_ptr(), _ptr(bias), float(eps), 1 if per_token else 0,
-                                                  xq.data_ptr(), _ptr(s_row), row_off.data_ptr(), M, K, _stream(x)), "asq_norm_quantize_off")
-        else:
-            L.check(L.lib().asq_norm_quantize(x.data_ptr(), _DT[x.dtype], weight.data_ptr(), _ptr(bias), float(eps), 1 if per_token else 0,
-                                              xq.data_ptr(), _ptr(s_row), M, K, _stream(x)), "asq_norm_quantize")
-    return (xq, s_row, row_off) if offsets else (xq, s_row)
+    _same_device(x, weight, bias)
+    return x.shape
+
+
+def norm_quantize(x, weight, bias=None, eps=1e-5, per_token=False, offsets=False):
+    """Fused (scale-folded) RMSNorm / LayerNorm -> int8 activation (SURVEY 8f N1).  x [M,K]; weight (and bias for
+    LayerNorm) [K] in x's dtype.  Returns (xq int8 [M,K], s_row f32 [M] or None); offsets=True emits the offset image
+    (asq_norm_quantize_off) and returns (xq', s_row, row_off int32 [M,2])."""
+    M, K = _norm_operands(x, weight, bias)
+    xq, s_row, row_off = _rows_out(M, K, x.device, per_token, offsets)
+    head = (x.data_ptr(), _DT[x.dtype], weight.data_ptr(), _ptr(bias), float(eps), 1 if per_token else 0, xq.data_ptr(), _ptr(s_row))
+    if offsets:
+        _launch("asq_norm_quantize_off", x.device, *head, row_off.data_ptr(), M, K, _stream(x))
+        return xq, s_row, row_off
+    _launch("asq_norm_quantize", x.device, *head, M, K, _stream(x))
+    return xq, s_row
 
 
 def add_norm_quantize(x, residual, weight, bias=None, eps=1e-5, per_token=False, out=None, offsets=False):
     """h = residual + x (in x's dtype) and the fused norm -> int8 of h in one pass (the reference's dq_add_layernorm_q,
     csrc/kernels/fused.cu:5-25, on a floating x).  Returns (h [M,K], xq int8 [M,K], s_row f32 [M] or None) -- with offsets=True (h, xq', s_row, row_off int32 [M,2]); `out`
     may be `residual` itself (the residual stream is updated in place).  offsets=True: xq is the offset image (asq_add_norm_quantize_off)."""
-    _dev(x, "x"), _dev(residual, "residual"), _dev(weight, "weight")
+    _dev(x, "x"), _dev(residual, "residual")
     if x.dtype not in _DT or x.dim() != 2 or residual.shape != x.shape or residual.dtype != x.dtype:
         raise ValueError("x and residual must be 2-D float tensors of equal shape and dtype")
-    if weight.dtype != x.dtype or weight.numel() != x.shape[1]:
-        raise ValueError("weight must be a [K] tensor of x's dtype")
-    if bias is not None:
-        _dev(bias, "bias")
-        if bias.dtype != x.dtype or bias.numel() != x.shape[1]:
-            raise ValueError("bias must match weight")
-    M, K = x.shape
-    h = torch.empty_like(x) if out is None else _dev(out, "out")
-    if h.shape != x.shape or h.dtype != x.dtype:
-        raise ValueError("out has wrong dtype/shape")
-    if out is not None:
-        _bump_version(out)
-    xq = torch.empty((M, K), dtype=torch.int8, device=x.device)
-    s_row = torch.empty((M,), dtype=torch.float32, device=x.device) if per_token else None
-    row_off = torch.empty((M, 2), dtype=torch.int32, device=x.device) if offsets else None
-    with _on(x.device):
-        if offsets:
-            L.check(L.lib().asq_add_norm_quantize_off(x.data_ptr(), residual.data_ptr(), h.data_ptr(), _DT[x.dtype], weight.data_ptr(), _ptr(bias), float(eps),
-                                                      1 if per_token else 0, xq.data_ptr(), _ptr(s_row), row_off.data_ptr(), M, K, _stream(x)), "asq_add_norm_quantize_off")
-        else:
-            L.check(L.lib().asq_add_norm_quantize(x.data_ptr(), residual.data_ptr(), h.data_ptr(), _DT[x.dtype], weight.data_ptr(), _ptr(bias), float(eps),
-                                                  1 if per_token else 0, xq.data_ptr(), _ptr(s_row), M, K, _stream(x)), "asq_add_norm_quantize")
-    return (h, xq, s_row, row_off) if offsets else (h, xq, s_row)
+    _same_device(x, residual)
+    M, K = _norm_operands(x, weight, bias)
+    h = _out(out, (M, K), x.dtype, x.device)
+    xq, s_row, row_off = _rows_out(M, K, x.device, per_token, offsets)
+    head = (x.data_ptr(), residual.data_ptr(), h.data_ptr(), _DT[x.dtype], weight.data_ptr(), _ptr(bias), float(eps), 1 if per_token else 0, xq.data_ptr(), _ptr(s_row))
+    if offsets:
+        _launch("asq_add_norm_quantize_off", x.device, *head, row_off.data_ptr(), M, K, _stream(x))
+        return h, xq, s_row, row_off
+    _launch("asq_add_norm_quantize", x.device, *head, M, K, _stream(x))
+    return h, xq, s_row
 
 
-SILU_EXACT_DEFAULT = os.environ.get("ASQ_SILU_EXACT", "0") == "1"   # the bit-reproducible SiLU everywhere `fast` is left to the default
+def _gate_and_up(gate, up, two_d=True):
+    _dev(gate, "gate"), _dev(up, "up")
+    if gate.dtype not in _DT or (two_d and gate.dim() != 2) or up.dtype != gate.dtype or up.shape != gate.shape:
+        raise ValueError(f"gate and up must be {'2-D ' if two_d else ''}float tensors of equal shape and dtype")
+    _same_device(gate, up)
 
 
 def silu_mul_quantize(gate, up, per_token=True, quant_scale=1.0, fast=None, offsets=False):
@@ -518,51 +522,28 @@ def silu_mul_quantize(gate, up, per_token=True, quant_scale=1.0, fast=None, offs
     fast (default True since round 5; ASQ_SILU_EXACT=1 flips the default): silu from the hardware transcendentals (C-ABI flag ASQ_SILU_FAST, ~1.5x the throughput: 5.3 vs 3.5 TB/s at
     65536 x 11008).  fast=False: the fixed-operation-order sequence oracle/n1.py reproduces bit for bit.  BOTH forms meet the same bound against what the reference's composition
     computes -- torch F.silu(gate) * up, then the consumer's quantiser: |diff| <= 1 int8 on < 2e-3 of the elements (tests/test_hip_harness.py::test_silu_mul_quant_matches_two_step_path)."""
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
-    _dev(gate, "gate"), _dev(up, "up")
-    if gate.dtype not in _DT or gate.dim() != 2 or up.dtype != gate.dtype or up.shape != gate.shape:
-        raise ValueError("gate and up must be 2-D float tensors of equal shape and dtype")
+    _gate_and_up(gate, up)
     M, K = gate.shape
-    xq = torch.empty((M, K), dtype=torch.int8, device=gate.device)
-    s_row = torch.empty((M,), dtype=torch.float32, device=gate.device) if per_token else None
-    row_off = torch.empty((M, 2), dtype=torch.int32, device=gate.device) if offsets else None
-    with _on(gate.device):
-        if offsets:
-            L.check(L.lib().asq_silu_mul_quantize_off(gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], (1 if per_token else 0) | (2 if fast else 0), float(quant_scale),
-                                                      xq.data_ptr(), _ptr(s_row), row_off.data_ptr(), M, K, _stream(gate)), "asq_silu_mul_quantize_off")
-        else:
-            L.check(L.lib().asq_silu_mul_quantize(gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], (1 if per_token else 0) | (2 if fast else 0), float(quant_scale),
-                                                  xq.data_ptr(), _ptr(s_row), M, K, _stream(gate)), "asq_silu_mul_quantize")
-    return (xq, s_row, row_off) if offsets else (xq, s_row)
+    xq, s_row, row_off = _rows_out(M, K, gate.device, per_token, offsets)
+    head = (gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], (1 if per_token else 0) | _silu_flag(fast), float(quant_scale), xq.data_ptr(), _ptr(s_row))
+    if offsets:
+        _launch("asq_silu_mul_quantize_off", gate.device, *head, row_off.data_ptr(), M, K, _stream(gate))
+        return xq, s_row, row_off
+    _launch("asq_silu_mul_quantize", gate.device, *head, M, K, _stream(gate))
+    return xq, s_row
 
 
 def linear_w8a8(xq, w, out_dtype, s_scalar=1.0, s_row=None, s_col=None, bias=None, order="scale_first", out=None):
     """Fused GEMM + dequant/bias epilogue: out[M,N] = (s_col|s_scalar)[*s_row] * f32(xq.w^T) + bias."""
-    _dev(xq, "xq"), _dev(w, "weight")
-    if xq.dtype != torch.int8 or w.dtype != torch.int8 or xq.dim() != 2 or w.dim() != 2 or xq.shape[1] != w.shape[1]:
-        raise ValueError("xq [M,K] and weight [N,K] must be int8 with equal K")
-    M, K = xq.shape
-    N = w.shape[0]
-    for name, t, n in (("s_row", s_row, M), ("s_col", s_col, N), ("bias", bias, N)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != n:
-                raise ValueError(f"{name} must be float32 with {n} elements")
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=xq.device)
-    else:
-        _dev(out, "out")
-        if out.dtype != out_dtype or tuple(out.shape) != (M, N):
-            raise ValueError("out has wrong dtype/shape")
-        _bump_version(out)
+    M, N, K = _pair(xq, w, torch.int8)
+    _vectors(s_row, s_col, bias, M, N)
+    out = _out(out, (M, N), out_dtype, xq.device)
     dev = _same_device(xq, w, out, s_row, s_col, bias)
     with _on(dev):
-        ws, n = _gemm_ws(M, N, K, dev, _stream(xq))
-        L.check(L.lib().asq_linear_w8a8(xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype], M, N, K, float(s_scalar),
-                                        _ptr(s_row), _ptr(s_col), _ptr(bias),
-                                        L.ASQ_EPI_SCALE_FIRST if order == "scale_first" else L.ASQ_EPI_ACC_FIRST, _ptr(ws), n, _stream(xq)),
-                "asq_linear_w8a8")
+        st = _stream(xq)
+        ws, n = _gemm_ws(M, N, K, dev, st)
+        _call("asq_linear_w8a8", xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype], M, N, K, float(s_scalar), _ptr(s_row), _ptr(s_col), _ptr(bias),
+              _epi_order(order), _ptr(ws), n, st)
     return out
 
 
@@ -570,25 +551,37 @@ def linear_w8a8_q8(xq, w, mid_dtype, s_scalar=1.0, s_row=None, s_col=None, bias=
                    order="scale_first"):
     """GEMM + dequant/bias + activation + the NEXT linear's per-tensor quantiser in one launch: returns int8 [M,N], bit-identical
     to linear_w8a8(..., mid_dtype) -> act -> quantize_act(..., qmode, quant_scale).  act in {None, "relu"}."""
-    _dev(xq, "xq"), _dev(w, "weight")
-    if xq.dtype != torch.int8 or w.dtype != torch.int8 or xq.dim() != 2 or w.dim() != 2 or xq.shape[1] != w.shape[1]:
-        raise ValueError("xq [M,K] and weight [N,K] must be int8 with equal K")
+    M, N, K = _pair(xq, w, torch.int8)
     if qmode not in ("per-tensor-round", "per-tensor-div") or act not in (None, "relu") or mid_dtype not in _DT:
         raise ValueError("qmode must be per-tensor-round / per-tensor-div, act None / 'relu', mid_dtype a float dtype")
-    M, K = xq.shape
-    N = w.shape[0]
-    for name, t, n in (("s_row", s_row, M), ("s_col", s_col, N), ("bias", bias, N)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != n:
-                raise ValueError(f"{name} must be float32 with {n} elements")
+    _vectors(s_row, s_col, bias, M, N)
     out = torch.empty((M, N), dtype=torch.int8, device=xq.device)
     dev = _same_device(xq, w, s_row, s_col, bias)
     with _on(dev):
-        ws, n = _gemm_ws(M, N, K, dev, _stream(xq))
-        L.check(L.lib().asq_linear_w8a8_q8(xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[mid_dtype], M, N, K, float(s_scalar), _ptr(s_row), _ptr(s_col),
-                                           _ptr(bias), L.ASQ_EPI_SCALE_FIRST if order == "scale_first" else L.ASQ_EPI_ACC_FIRST, 1 if act == "relu" else 0,
-                                           _ACT[qmode], float(quant_scale), _ptr(ws), n, _stream(xq)), "asq_linear_w8a8_q8")
+        st = _stream(xq)
+        ws, n = _gemm_ws(M, N, K, dev, st)
+        _call("asq_linear_w8a8_q8", xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[mid_dtype], M, N, K, float(s_scalar), _ptr(s_row), _ptr(s_col), _ptr(bias),
+              _epi_order(order), 1 if act == "relu" else 0, _ACT[qmode], float(quant_scale), _ptr(ws), n, st)
+    return out
+
+
+def _grouped(xq, w, group_offsets, s_group, out_dtype, s_row, bias, images=None):
+    """linear_w8a8_grouped (images None) and linear_w8a8_grouped_off (images = (row_off, col_off))"""
+    M, N, K, G = _pair(xq, w, torch.int8, stack=True)
+    _operand(group_offsets, "group_offsets", torch.int32, G + 1), _operand(s_group, "s_group", torch.float32, G)
+    if images is not None:
+        _offsets(*images, M, G * N)
+    _operand(s_row, "s_row", torch.float32, M, optional=True), _operand(bias, "bias", torch.float32, G * N, optional=True)
+    out = torch.empty((M, N), dtype=out_dtype, device=xq.device)
+    dev = _same_device(xq, w, group_offsets, s_group, s_row, bias, *(images or ()))
+    with _on(dev):
+        st = _stream(xq)
+        ws, n = _grouped_ws(L.lib(), M, N, K, G, dev, st)
+        head = (xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, N, K, s_group.data_ptr(), _ptr(s_row), _ptr(bias))
+        if images is None:
+            _call("asq_linear_w8a8_grouped_ws", *head, _ptr(ws), n, st)
+        else:
+            _call("asq_linear_w8a8_grouped_off", *head, images[0].data_ptr(), images[1].data_ptr(), _ptr(ws), n, st)
     return out
 
 
@@ -597,26 +590,7 @@ def linear_w8a8_grouped(xq, w, group_offsets, s_group, out_dtype, s_row=None, bi
     w int8 [G,N,K], group_offsets int32 [G+1] on the device, s_group f32 [G] on the device (each expert's
     dequant_scale), s_row f32 [M] (per-token) or None, bias f32 [G,N] or None.  Row m of the result is
     bit-identical to linear_w8a8 on its group's slice."""
-    _dev(xq, "xq"), _dev(w, "weight"), _dev(group_offsets, "group_offsets"), _dev(s_group, "s_group")
-    if xq.dtype != torch.int8 or w.dtype != torch.int8 or xq.dim() != 2 or w.dim() != 3 or xq.shape[1] != w.shape[2]:
-        raise ValueError("xq [M,K] int8 and weight [G,N,K] int8 with equal K expected")
-    M, K = xq.shape
-    G, N = w.shape[0], w.shape[1]
-    if group_offsets.dtype != torch.int32 or group_offsets.numel() != G + 1 or s_group.dtype != torch.float32 or s_group.numel() != G:
-        raise ValueError("group_offsets must be int32 [G+1] and s_group float32 [G]")
-    for name, t, n in (("s_row", s_row, M), ("bias", bias, G * N)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != n:
-                raise ValueError(f"{name} must be float32 with {n} elements")
-    out = torch.empty((M, N), dtype=out_dtype, device=xq.device)
-    dev = _same_device(xq, w, group_offsets, s_group, s_row, bias)
-    with _on(dev):
-        lib, st = L.lib(), _stream(xq)
-        ws, n = _grouped_ws(lib, M, N, K, G, dev, st)
-        L.check(lib.asq_linear_w8a8_grouped_ws(xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, N, K,
-                                               s_group.data_ptr(), _ptr(s_row), _ptr(bias), _ptr(ws), n, st), "asq_linear_w8a8_grouped")
-    return out
+    return _grouped(xq, w, group_offsets, s_group, out_dtype, s_row, bias)
 
 
 def grouped_offsets_supported(M, N, K, out_dtype):
@@ -628,65 +602,17 @@ def grouped_offsets_supported(M, N, K, out_dtype):
 def linear_w8a8_grouped_off(xq_off, w_off, row_off, col_off, group_offsets, s_group, out_dtype, s_row=None, bias=None):
     """linear_w8a8_grouped on offset operand images: xq_off / row_off from a *_off quantiser, w_off [G,N,K] / col_off [G,N,2] from weight_offset_image on the
     stack viewed as [G*N, K].  Bit-identical to linear_w8a8_grouped on the plain operands."""
-    _dev(xq_off, "xq"), _dev(w_off, "weight"), _dev(group_offsets, "group_offsets"), _dev(s_group, "s_group"), _dev(row_off, "row_off"), _dev(col_off, "col_off")
-    if xq_off.dtype != torch.int8 or w_off.dtype != torch.int8 or xq_off.dim() != 2 or w_off.dim() != 3 or xq_off.shape[1] != w_off.shape[2]:
-        raise ValueError("xq [M,K] int8 and weight [G,N,K] int8 with equal K expected")
-    M, K = xq_off.shape
-    G, N = w_off.shape[0], w_off.shape[1]
-    if group_offsets.dtype != torch.int32 or group_offsets.numel() != G + 1 or s_group.dtype != torch.float32 or s_group.numel() != G:
-        raise ValueError("group_offsets must be int32 [G+1] and s_group float32 [G]")
-    if row_off.dtype != torch.int32 or row_off.numel() != 2 * M or col_off.dtype != torch.int32 or col_off.numel() != 2 * G * N:
-        raise ValueError("row_off must be int32 [M,2] and col_off int32 [G,N,2]")
-    for name, t, n in (("s_row", s_row, M), ("bias", bias, G * N)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != n:
-                raise ValueError(f"{name} must be float32 with {n} elements")
-    out = torch.empty((M, N), dtype=out_dtype, device=xq_off.device)
-    dev = _same_device(xq_off, w_off, group_offsets, s_group, s_row, bias, row_off, col_off)
-    with _on(dev):
-        lib, st = L.lib(), _stream(xq_off)
-        ws, n = _grouped_ws(lib, M, N, K, G, dev, st)
-        L.check(lib.asq_linear_w8a8_grouped_off(xq_off.data_ptr(), w_off.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, N, K,
-                                                s_group.data_ptr(), _ptr(s_row), _ptr(bias), row_off.data_ptr(), col_off.data_ptr(), _ptr(ws), n, st), "asq_linear_w8a8_grouped_off")
-    return out
+    return _grouped(xq_off, w_off, group_offsets, s_group, out_dtype, s_row, bias, (row_off, col_off))
 
 
 def linear_w8a8_forward(x2d, w, act_mode, quant_scale, s_scalar, s_col=None, bias=None, image=None):
     """Whole module forward on a 2-D activation: quantise -> GEMM + epilogue, one stream,
     no int32 round trip.  Returns out [M,N] in x's dtype.  image = (w_off, col_off) of this weight (weight_offset_image) or None: with it the C-ABI
     runs the shapes it gives to the 256 x 256 kernel on offset operand images (same bits, less energy)."""
-    _dev(x2d, "x"), _dev(w, "weight")
-    if x2d.dtype not in _DT:
-        raise ValueError(f"unsupported activation dtype {x2d.dtype}")
-    if w.dtype != torch.int8 or x2d.dim() != 2 or w.dim() != 2 or x2d.shape[1] != w.shape[1]:
-        raise ValueError(f"shape/dtype mismatch: x {tuple(x2d.shape)} {x2d.dtype}, weight {tuple(w.shape)} {w.dtype}")
-    M, K = x2d.shape
-    N = w.shape[0]
-    for name, t in (("s_col", s_col), ("bias", bias)):
-        if t is not None:
-            _dev(t, name)
-            if t.dtype != torch.float32 or t.numel() != N:
-                raise ValueError(f"{name} must be float32 with {N} elements")
-    dev = _same_device(x2d, w, s_col, bias)
+    M, N, K, dev = _forward_operands(x2d, w, s_col, bias)
     if image is not None:
         _check_image(image, N, K, dev)
-    out = torch.empty((M, N), dtype=x2d.dtype, device=dev)
-    if M == 0 or N == 0:
-        return out
-    lib = L.lib()
-    stream = _stream(x2d)
-    ws, nbytes = _forward_ws(lib, M, N, K, dev, stream)
-    with _on(dev):
-        if image is not None:
-            L.check(lib.asq_linear_w8a8_forward_off(x2d.data_ptr(), _DT[x2d.dtype], w.data_ptr(), image[0].data_ptr(), image[1].data_ptr(), out.data_ptr(), M, N, K,
-                                                    _ACT[act_mode], float(quant_scale), float(s_scalar), _ptr(s_col), _ptr(bias),
-                                                    ws.data_ptr(), nbytes, stream), "asq_linear_w8a8_forward_off")
-        else:
-            L.check(lib.asq_linear_w8a8_forward(x2d.data_ptr(), _DT[x2d.dtype], w.data_ptr(), out.data_ptr(), M, N, K,
-                                                _ACT[act_mode], float(quant_scale), float(s_scalar), _ptr(s_col), _ptr(bias),
-                                                ws.data_ptr(), nbytes, stream), "asq_linear_w8a8_forward")
-    return out
+    return linear_w8a8_forward_trusted(x2d, w, _ACT[act_mode], float(quant_scale), float(s_scalar), s_col, bias, image, N, K)
 
 
 def linear_w8a8_forward_trusted(x2d, w, act_code, quant_scale, s_scalar, s_col, bias, image, N, K):
@@ -708,8 +634,8 @@ def linear_w8a8_forward_trusted(x2d, w, act_code, quant_scale, s_scalar, s_col, 
         return out
     lib = L.lib()
     stream = _stream(x2d)
-    ws, nbytes = _forward_ws(lib, M, N, K, dev, stream)
-    with _on(dev):
+    with _on(dev):   # (hand-written, not _call: the decode hot path.  The workspace is fetched INSIDE the guard: its first use on a stream launches asq_workspace_init)
+        ws, nbytes = _forward_ws(lib, M, N, K, dev, stream)
         if image is not None:
             rc = lib.asq_linear_w8a8_forward_off(x2d.data_ptr(), dt, w.data_ptr(), image[0].data_ptr(), image[1].data_ptr(), out.data_ptr(), M, N, K, act_code, quant_scale, s_scalar,
                                                  None if s_col is None else s_col.data_ptr(), None if bias is None else bias.data_ptr(), ws.data_ptr(), nbytes, stream)
@@ -717,7 +643,7 @@ def linear_w8a8_forward_trusted(x2d, w, act_code, quant_scale, s_scalar, s_col, 
             rc = lib.asq_linear_w8a8_forward(x2d.data_ptr(), dt, w.data_ptr(), out.data_ptr(), M, N, K, act_code, quant_scale, s_scalar,
                                              None if s_col is None else s_col.data_ptr(), None if bias is None else bias.data_ptr(), ws.data_ptr(), nbytes, stream)
     if rc:
-        L.check(rc, "asq_linear_w8a8_forward")
+        L.check(rc, "asq_linear_w8a8_forward" if image is None else "asq_linear_w8a8_forward_off")
     return out
 
 
@@ -729,10 +655,7 @@ def quantize_act_fp8(x, mode, static_scale=1.0):
     device; "per-tensor" (dynamic): scale f32 0-dim ON THE DEVICE (no host sync, like the reference's
     0-dim scale tensor); "static": scale is the given host value (returned as a python float).
     Reference: layers/functional/quantization.py:144-211."""
-    _dev(x, "x")
-    if x.dtype not in _DT or x.dim() != 2:
-        raise ValueError("x must be a 2-D float32/float16/bfloat16 tensor")
-    M, K = x.shape
+    M, K = _float_rows(x)
     xq = torch.empty((M, K), dtype=torch.uint8, device=x.device)
     if mode == "per-token":
         sc = torch.empty((M,), dtype=torch.float32, device=x.device)
@@ -740,9 +663,7 @@ def quantize_act_fp8(x, mode, static_scale=1.0):
         sc = torch.empty((2,), dtype=torch.float32, device=x.device)
     else:
         sc = None
-    with _on(x.device):
-        L.check(L.lib().asq_quantize_act_fp8(x.data_ptr(), _DT[x.dtype], _FP8[mode], float(static_scale), xq.data_ptr(), _ptr(sc), M, K,
-                                             _stream(x)), "asq_quantize_act_fp8")
+    _launch("asq_quantize_act_fp8", x.device, x.data_ptr(), _DT[x.dtype], _FP8[mode], float(static_scale), xq.data_ptr(), _ptr(sc), M, K, _stream(x))
     xq = xq.view(torch.float8_e4m3fn)
     if mode == "per-token":
         return xq, sc.view(M, 1)
@@ -754,27 +675,18 @@ def quantize_act_fp8(x, mode, static_scale=1.0):
 def rmsnorm(x, weight, eps=1e-5):
     """y = weight * dt(f32(x) * rsqrt(mean(x^2) + eps)) in ONE pass (asq_rmsnorm): HF LlamaRMSNorm's arithmetic with a floating output -- the norm as a module of its own, as
     the reference's composition has it (models/llama.py:27-37); the N1 form norm_quantize emits int8 instead.  x [M,K], weight [K] of x's dtype."""
-    _dev(x, "x"), _dev(weight, "weight")
-    if x.dtype not in _DT or x.dim() != 2 or weight.dtype != x.dtype or weight.numel() != x.shape[1]:
-        raise ValueError("x must be 2-D float and weight a [K] tensor of the same dtype")
-    M, K = x.shape
+    M, K = _norm_operands(x, weight, None)
     y = torch.empty_like(x)
-    with _on(x.device):
-        L.check(L.lib().asq_rmsnorm(x.data_ptr(), _DT[x.dtype], weight.data_ptr(), float(eps), y.data_ptr(), M, K, _stream(x)), "asq_rmsnorm")
+    _launch("asq_rmsnorm", x.device, x.data_ptr(), _DT[x.dtype], weight.data_ptr(), float(eps), y.data_ptr(), M, K, _stream(x))
     return y
 
 
 def silu_mul(gate, up, fast=None):
     """silu(gate) * up in the activation dtype in ONE pass (asq_silu_mul): dt(dt(silu(g)) * u), the two roundings of F.silu(gate) * up -- the gated activation as an op of
     its own, as the reference's composition has it (HF LlamaMLP); the N1 form silu_mul_quantize emits int8 instead.  gate / up: contiguous tensors of one shape and dtype."""
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
-    _dev(gate, "gate"), _dev(up, "up")
-    if gate.dtype not in _DT or up.dtype != gate.dtype or up.shape != gate.shape:
-        raise ValueError("gate and up must be float tensors of equal shape and dtype")
+    _gate_and_up(gate, up, two_d=False)
     out = torch.empty_like(gate)
-    with _on(gate.device):
-        L.check(L.lib().asq_silu_mul(gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], L.ASQ_SILU_FAST if fast else 0, out.data_ptr(), gate.numel(), _stream(gate)), "asq_silu_mul")
+    _launch("asq_silu_mul", gate.device, gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], _silu_flag(fast), out.data_ptr(), gate.numel(), _stream(gate))
     return out
 
 
@@ -783,7 +695,6 @@ def rope(x, cos, sin, out=None):
     (strides (S * ld, ld, D, 1) with ld >= H * D); cos / sin [S, D/2] of x's dtype, positions 0 .. S-1, rotate_half convention.  Returns a DENSE [B, S, H, D] tensor
     (out=x rotates a dense x in place).  fp16: bit-identical to the torch composition addcmul(x1 * cos, x2, sin, value=-1) / addcmul(x2 * cos, x1, sin) it replaces
     (harness._rope_torch); bf16: the same operations at fp32 width."""
-    _dev(cos, "cos"), _dev(sin, "sin")
     if not isinstance(x, torch.Tensor) or not x.is_cuda:   # (x may be a strided slice: _dev's contiguity check does not apply)
         raise RuntimeError("x must be a HIP (cuda:N) tensor; there is no CPU fallback")
     if x.dtype not in _DT or x.dim() != 4:
@@ -793,14 +704,9 @@ def rope(x, cos, sin, out=None):
     ld = st[1] if S > 1 else (st[0] if B > 1 else H * D)
     if not (st[3] == 1 and st[2] == D and ld >= H * D and (B == 1 or S == 1 or st[0] == S * ld)) or (S == 1 and B > 1 and st[0] < H * D):
         raise ValueError("x must be [B, S, H, D] with H * D contiguous and one row pitch (a projection output or a slice of a fused one)")
-    if cos.dtype != x.dtype or sin.dtype != x.dtype or cos.numel() != S * (D // 2) or sin.numel() != S * (D // 2) or not (cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError("cos / sin must be contiguous [S, D/2] tables of x's dtype")
-    if out is None:
-        out = torch.empty((B, S, H, D), dtype=x.dtype, device=x.device)
-    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a dense tensor of x's shape, dtype and device")
-    with _on(x.device):
-        L.check(L.lib().asq_rope(x.data_ptr(), ld, out.data_ptr(), _DT[x.dtype], cos.data_ptr(), sin.data_ptr(), B, S, H, D, _stream(x)), "asq_rope")
+    _operand(cos, "cos", x.dtype, S * (D // 2)), _operand(sin, "sin", x.dtype, S * (D // 2))   # ([S, D/2] tables of x's dtype)
+    out = _out(out, (B, S, H, D), x.dtype, x.device)
+    _launch("asq_rope", _same_device(x, cos, sin), x.data_ptr(), ld, out.data_ptr(), _DT[x.dtype], cos.data_ptr(), sin.data_ptr(), B, S, H, D, _stream(x))
     return out
 
 
@@ -808,19 +714,11 @@ def silu_mul_quantize_fp8(gate, up, fast=None):
     """e4m3(per-token quantise(silu(gate) * up)) in ONE pass (asq_silu_mul_quantize_fp8): (xq float8_e4m3fn [M,K], scale f32 [M,1]) -- what
     quantize_act_fp8(F.silu(gate) * up, "per-token") returns from three.  fast as in silu_mul_quantize (default: the hardware-transcendental SiLU; False: the
     fixed-operation-order form oracle/n1.py::silu_mul_quant_fp8_kernel_order repeats bit for bit).  Reference: models/mixtral.py:99-101 on FP8LinearDynamic modules."""
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
-    _dev(gate, "gate"), _dev(up, "up")
-    if gate.dtype not in _DT or gate.dim() != 2 or up.dtype != gate.dtype or up.shape != gate.shape:
-        raise ValueError("gate and up must be 2-D float tensors of equal shape and dtype")
-    if not (gate.is_contiguous() and up.is_contiguous()):
-        raise ValueError("gate / up must be contiguous")
+    _gate_and_up(gate, up)
     M, K = gate.shape
     xq = torch.empty((M, K), dtype=torch.uint8, device=gate.device)
     sc = torch.empty((M,), dtype=torch.float32, device=gate.device)
-    with _on(gate.device):
-        L.check(L.lib().asq_silu_mul_quantize_fp8(gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], L.ASQ_SILU_FAST if fast else 0, xq.data_ptr(), sc.data_ptr(), M, K,
-                                                  _stream(gate)), "asq_silu_mul_quantize_fp8")
+    _launch("asq_silu_mul_quantize_fp8", gate.device, gate.data_ptr(), up.data_ptr(), _DT[gate.dtype], _silu_flag(fast), xq.data_ptr(), sc.data_ptr(), M, K, _stream(gate))
     return xq.view(torch.float8_e4m3fn), sc.view(M, 1)
 
 
@@ -828,28 +726,27 @@ def fp8_grouped_gate_up_supported(M, F, K, out_dtype):
     return out_dtype in _DT and bool(L.lib().asq_fp8_grouped_gate_up_supported(int(M), int(F), int(K), _DT[out_dtype]))
 
 
+def _fp8_grouped_operands(xq, a_scale, w, wname, group_offsets, even=False, **group_scales):
+    """operands of the grouped fp8 launches: xq e4m3 [M,K], the stack e4m3 [G,N,K], a_scale f32 [M] (or [M,1]), group_offsets int32 [G+1], f32 [G] scale
+    vectors by name -> (M, N, K, G)"""
+    M, N, K, G = _pair(xq, w, torch.float8_e4m3fn, "xq", wname, stack=True, even=even)
+    _operand(group_offsets, "group_offsets", torch.int32, G + 1), _operand(a_scale, "a_scale", torch.float32, M)
+    for name, t in group_scales.items():
+        _operand(t, name, torch.float32, G)
+    return M, N, K, G
+
+
 def linear_fp8_grouped_gate_up(xq, a_scale, w_gu, group_offsets, s_gate, s_up, out_dtype, fast=None):
     """SiLU(w1 x) * (w3 x) of ALL groups in ONE grouped fp8 launch over the interleaved stacks w_gu [G, 2F, K] (interleave_gate_up_stack of two float8_e4m3fn stacks: blocks
     of 32 channels; asq_linear_fp8_grouped_gate_up): out [M, F], bit-identical to linear_fp8_grouped (w1), (w3) and the SiLU * up of silu_mul_quantize_fp8(fast=...).
     xq float8_e4m3fn [M, K] + a_scale f32 [M] or [M, 1] (quantize_act_fp8 per-token); s_gate / s_up f32 [G] on the device."""
-    if fast is None:
-        fast = not SILU_EXACT_DEFAULT
-    _dev(xq, "xq"), _dev(w_gu, "w_gu"), _dev(group_offsets, "group_offsets"), _dev(s_gate, "s_gate"), _dev(s_up, "s_up"), _dev(a_scale, "a_scale")
-    if xq.dtype != torch.float8_e4m3fn or w_gu.dtype != torch.float8_e4m3fn or xq.dim() != 2 or w_gu.dim() != 3 or xq.shape[1] != w_gu.shape[2] or w_gu.shape[1] % 2:
-        raise ValueError("xq [M,K] and w_gu [G,2F,K] must be float8_e4m3fn with equal K")
-    M, K = xq.shape
-    G, F_ = w_gu.shape[0], w_gu.shape[1] // 2
-    if group_offsets.dtype != torch.int32 or group_offsets.numel() != G + 1:
-        raise ValueError("group_offsets must be int32 with G + 1 elements")
-    for name, t, n in (("a_scale", a_scale, M), ("s_gate", s_gate, G), ("s_up", s_up, G)):
-        if t.dtype != torch.float32 or t.numel() != n:
-            raise ValueError(f"{name} must be float32 with {n} elements")
+    M, N, K, G = _fp8_grouped_operands(xq, a_scale, w_gu, "w_gu", group_offsets, even=True, s_gate=s_gate, s_up=s_up)
+    F_ = N // 2
     if not fp8_grouped_gate_up_supported(M, F_, K, out_dtype):
         raise ValueError("shape not supported by the grouped fp8 gate || up launch (fp8_grouped_gate_up_supported)")
     out = torch.empty((M, F_), dtype=out_dtype, device=xq.device)
-    with _on(xq.device):
-        L.check(L.lib().asq_linear_fp8_grouped_gate_up(xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, F_, K, a_scale.data_ptr(),
-                                                       s_gate.data_ptr(), s_up.data_ptr(), L.ASQ_SILU_FAST if fast else 0, _stream(xq)), "asq_linear_fp8_grouped_gate_up")
+    _launch("asq_linear_fp8_grouped_gate_up", _same_device(xq, w_gu, group_offsets, a_scale, s_gate, s_up), xq.data_ptr(), w_gu.data_ptr(), out.data_ptr(), _DT[out_dtype],
+            group_offsets.data_ptr(), G, M, F_, K, a_scale.data_ptr(), s_gate.data_ptr(), s_up.data_ptr(), _silu_flag(fast), _stream(xq))
     return out
 
 
@@ -862,44 +759,32 @@ def quantize_mxfp8(x):
     M, K = x.shape
     xq = torch.empty((M, K), dtype=torch.uint8, device=x.device)
     sc = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
-    with _on(x.device):
-        L.check(L.lib().asq_quantize_mxfp8(x.data_ptr(), _DT[x.dtype], xq.data_ptr(), sc.data_ptr(), M, K, _stream(x)), "asq_quantize_mxfp8")
+    _launch("asq_quantize_mxfp8", x.device, x.data_ptr(), _DT[x.dtype], xq.data_ptr(), sc.data_ptr(), M, K, _stream(x))
     return xq.view(torch.float8_e4m3fn), sc
 
 
 def linear_mxfp8(xq, x_scales, wq, w_scales, out_dtype, bias=None):
     """out[M,N] = block-scaled e4m3 product of (xq, x_scales) [M,K] and (wq, w_scales) [N,K] (+ bias) on the scaled matrix-core instruction."""
-    for name, t in (("xq", xq), ("x_scales", x_scales), ("wq", wq), ("w_scales", w_scales)):
-        _dev(t, name)
+    _dev(xq, "xq"), _dev(wq, "wq")
     if xq.dim() != 2 or wq.dim() != 2 or xq.shape[1] != wq.shape[1] or xq.shape[1] % 64 != 0 or xq.element_size() != 1 or wq.element_size() != 1:
         raise ValueError("xq [M,K] and wq [N,K] must be 1-byte e4m3 tensors with equal K, K % 64 == 0")
     M, K = xq.shape
     N = wq.shape[0]
-    if tuple(x_scales.shape) != (M, K // 32) or tuple(w_scales.shape) != (N, K // 32) or x_scales.dtype != torch.uint8 or w_scales.dtype != torch.uint8:
-        raise ValueError("scales must be uint8 [rows, K/32]")
-    if bias is not None:
-        _dev(bias, "bias")
-        if bias.dtype != torch.float32 or bias.numel() != N:
-            raise ValueError(f"bias must be float32 with {N} elements")
+    _operand(x_scales, "x_scales", torch.uint8, shape=(M, K // 32)), _operand(w_scales, "w_scales", torch.uint8, shape=(N, K // 32))   # (E8M0 scales [rows, K/32])
+    _operand(bias, "bias", torch.float32, N, optional=True)
     out = torch.empty((M, N), dtype=out_dtype, device=xq.device)
     if M == 0 or N == 0:
         return out
-    dev = _same_device(xq, x_scales, wq, w_scales, bias)
-    with _on(dev):
-        L.check(L.lib().asq_linear_mxfp8(xq.data_ptr(), x_scales.data_ptr(), wq.data_ptr(), w_scales.data_ptr(), out.data_ptr(), _DT[out_dtype], M, N, K,
-                                         _ptr(bias), _stream(xq)), "asq_linear_mxfp8")
+    _launch("asq_linear_mxfp8", _same_device(xq, x_scales, wq, w_scales, bias), xq.data_ptr(), x_scales.data_ptr(), wq.data_ptr(), w_scales.data_ptr(), out.data_ptr(),
+            _DT[out_dtype], M, N, K, _ptr(bias), _stream(xq))
     return out
 
 
 def cast_e5m2(x):
     """x [M,K] f32/f16/bf16 -> float8_e5m2 [M,K], plain round-to-nearest-even cast (FP8E5M2Linear, linear.py:612)."""
-    _dev(x, "x")
-    if x.dtype not in _DT or x.dim() != 2:
-        raise ValueError("x must be a 2-D float32/float16/bfloat16 tensor")
-    M, K = x.shape
+    M, K = _float_rows(x)
     xq = torch.empty((M, K), dtype=torch.uint8, device=x.device)
-    with _on(x.device):
-        L.check(L.lib().asq_cast_e5m2(x.data_ptr(), _DT[x.dtype], xq.data_ptr(), M * K, _stream(x)), "asq_cast_e5m2")
+    _launch("asq_cast_e5m2", x.device, x.data_ptr(), _DT[x.dtype], xq.data_ptr(), M * K, _stream(x))
     return xq.view(torch.float8_e5m2)
 
 
@@ -927,14 +812,9 @@ def linear_fp8(xq, a_scale, w, w_scale, bias, out_dtype):
             a_host = float(a_scale)
     else:
         a_host = float(a_scale)
-    if bias is not None:
-        _dev(bias, "bias")
-        if bias.dtype != torch.float32 or bias.numel() != N:
-            raise ValueError(f"bias must be float32 with {N} elements")
-    dev = _same_device(xq, w, a_dev, bias)
-    with _on(dev):
-        L.check(L.lib().asq_linear_fp8(xq.data_ptr(), w.data_ptr(), fmt, out.data_ptr(), _DT[out_dtype], M, N, K, _ptr(a_dev), per_token,
-                                       a_host, float(w_scale), _ptr(bias), _stream(xq)), "asq_linear_fp8")
+    _operand(bias, "bias", torch.float32, N, optional=True)
+    _launch("asq_linear_fp8", _same_device(xq, w, a_dev, bias), xq.data_ptr(), w.data_ptr(), fmt, out.data_ptr(), _DT[out_dtype], M, N, K, _ptr(a_dev), per_token,
+            a_host, float(w_scale), _ptr(bias), _stream(xq))
     return out
 
 
@@ -951,7 +831,7 @@ def _bmm(a, b, alpha, out_kind, flags=0, b_group=1, out_token=False, heads=None)
     ASQ_BMM_* flags of the call.  With ASQ_BMM_B_KN among them b is [B, K, N] and the flag may be set on out_kind as well.  b_group = r (1 .. 256): b has
     B / r entries and entry i of a uses b[i // r] (ASQ_BMM_B_GROUP).  A 4-D a or b, or out_token, is token-major (ASQ_BMM_*_TOKEN): see _bmm_token."""
     kn = bool(flags & L.ASQ_BMM_B_KN)
-    _dev(a, "a"), _dev(b, "b")
+    _operand(a, "a"), _operand(b, "b")
     if a.dtype != torch.int8 or b.dtype != torch.int8:
         raise RuntimeError(f"expected int8 a and b, got {a.dtype} and {b.dtype}")
     if not (isinstance(b_group, int) and 1 <= b_group <= 256):
@@ -977,8 +857,7 @@ def _bmm(a, b, alpha, out_kind, flags=0, b_group=1, out_token=False, heads=None)
         N = b.shape[2 if kn else 1]
         out_shape = (B, M, N)
     out = torch.empty(out_shape, dtype=_BMM_DTYPE[kind], device=dev)
-    with _on(dev):
-        L.check(L.lib().asq_bmm_i8(a.data_ptr(), b.data_ptr(), out.data_ptr(), kind | flags, B, M, N, K, float(alpha), _stream(a)), "asq_bmm_i8")
+    _launch("asq_bmm_i8", dev, a.data_ptr(), b.data_ptr(), out.data_ptr(), kind | flags, B, M, N, K, float(alpha), _stream(a))
     return out
 
 
@@ -1092,9 +971,9 @@ def linear_i8_bias(x, w, bias, kind, alpha=1.0, beta=1.0):
     bias = bias.contiguous()
     out = torch.empty((M, N), dtype=out_dt, device=dev)
     with _on(dev):
-        ws, n = _gemm_ws(M, N, K, dev, _stream(x))
-        L.check(L.lib().asq_linear_i8_bias(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), kind, M, N, K, float(alpha), float(beta),
-                                           _ptr(ws), n, _stream(x)), "asq_linear_i8_bias")
+        st = _stream(x)
+        ws, n = _gemm_ws(M, N, K, dev, st)
+        _call("asq_linear_i8_bias", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), kind, M, N, K, float(alpha), float(beta), _ptr(ws), n, st)
     return out
 
 
@@ -1116,15 +995,13 @@ def dq_add_layernorm_q(x, x_scale, residual, gamma, beta, eps=1e-5):
     K = x.shape[-1]
     if gamma.dim() != 1 or beta.dim() != 1 or gamma.shape[0] != K or beta.shape[0] != K:
         raise ValueError(f"gamma and beta must be [{K}], got {tuple(gamma.shape)} and {tuple(beta.shape)}")
-    for t, name in ((x, "input"), (residual, "residual"), (gamma, "gamma"), (beta, "beta")):
-        _dev(t, name)
+    _operand(x, "input"), _operand(residual, "residual"), _operand(gamma, "gamma"), _operand(beta, "beta")
     dev = _same_device(x, residual, gamma, beta)
     h = torch.empty_like(residual)
     q = torch.empty(tuple(x.shape), dtype=torch.int8, device=dev)
     M = x.numel() // K if K else 0
-    with _on(dev):
-        L.check(L.lib().asq_dq_add_layernorm_q(x.data_ptr(), float(x_scale), residual.data_ptr(), h.data_ptr(), _DT[residual.dtype], gamma.data_ptr(),
-                                               beta.data_ptr(), float(eps), q.data_ptr(), M, K, _stream(x)), "asq_dq_add_layernorm_q")
+    _launch("asq_dq_add_layernorm_q", dev, x.data_ptr(), float(x_scale), residual.data_ptr(), h.data_ptr(), _DT[residual.dtype], gamma.data_ptr(), beta.data_ptr(), float(eps),
+            q.data_ptr(), M, K, _stream(x))
     return h, q
 
 
@@ -1132,25 +1009,11 @@ def linear_fp8_grouped(xq, a_scale, w, w_scale_group, group_offsets, out_dtype, 
     """ngroups independent e4m3 linears in one launch (Mixtral experts, FP8LinearDynamic math).  xq float8_e4m3fn [M,K]
     rows sorted by group, a_scale f32 [M] or [M,1] (per-token, device), w float8_e4m3fn [G,N,K], w_scale_group f32 [G]
     (device), group_offsets int32 [G+1] (device), bias f32 [G,N] or None."""
-    _dev(xq, "xq"), _dev(w, "weight"), _dev(group_offsets, "group_offsets"), _dev(w_scale_group, "w_scale_group"), _dev(a_scale, "a_scale")
-    f8 = torch.float8_e4m3fn
-    if xq.dtype != f8 or w.dtype != f8 or xq.dim() != 2 or w.dim() != 3 or xq.shape[1] != w.shape[2]:
-        raise ValueError("xq [M,K] and weight [G,N,K] must be float8_e4m3fn with equal K")
-    M, K = xq.shape
-    G, N = w.shape[0], w.shape[1]
-    if group_offsets.dtype != torch.int32 or group_offsets.numel() != G + 1 or w_scale_group.dtype != torch.float32 or w_scale_group.numel() != G:
-        raise ValueError("group_offsets must be int32 [G+1] and w_scale_group float32 [G]")
-    if a_scale.dtype != torch.float32 or a_scale.numel() != M:
-        raise ValueError("a_scale must be float32 with M elements (per-token)")
-    if bias is not None:
-        _dev(bias, "bias")
-        if bias.dtype != torch.float32 or bias.numel() != G * N:
-            raise ValueError(f"bias must be float32 with {G * N} elements")
+    M, N, K, G = _fp8_grouped_operands(xq, a_scale, w, "weight", group_offsets, w_scale_group=w_scale_group)
+    _operand(bias, "bias", torch.float32, G * N, optional=True)
     out = torch.empty((M, N), dtype=out_dtype, device=xq.device)
     if M == 0 or N == 0:
         return out
-    dev = _same_device(xq, w, group_offsets, w_scale_group, a_scale, bias)
-    with _on(dev):
-        L.check(L.lib().asq_linear_fp8_grouped(xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype], group_offsets.data_ptr(), G, M, N, K,
-                                               a_scale.data_ptr(), w_scale_group.data_ptr(), _ptr(bias), _stream(xq)), "asq_linear_fp8_grouped")
+    _launch("asq_linear_fp8_grouped", _same_device(xq, w, group_offsets, w_scale_group, a_scale, bias), xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype],
+            group_offsets.data_ptr(), G, M, N, K, a_scale.data_ptr(), w_scale_group.data_ptr(), _ptr(bias), _stream(xq))
     return out

@@ -1,5 +1,13 @@
-import time, torch, sys
-sys.path.insert(0, '/root/repo')
+"""Host time per call at decode sizes: the module call, the bare C-ABI call under it, and the general-checker ops.
+    python tools/pyoverhead.py [--root CHECKOUT] [--brief]
+--root: measure the package of another checkout (an A/B of two versions of the Python layer); --brief: the timed loops only."""
+import argparse, os, sys, time
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--brief", action="store_true")
+opt = ap.parse_args()
+sys.path.insert(0, opt.root)
+import torch
 from autosmoothquant_amd.layers.nn.linear import W8A8BFP32OFP32Linear
 from autosmoothquant_amd import ops
 dev = torch.device('cuda:0')
@@ -9,26 +17,28 @@ m = m.to(dev)
 x = torch.randn(32, 4096, device=dev, dtype=torch.float16)
 for _ in range(20): m(x)
 torch.cuda.synchronize()
-import cProfile, pstats
 t0 = time.perf_counter()
 for _ in range(2000): m(x)
 t1 = time.perf_counter()
 torch.cuda.synchronize()
 t2 = time.perf_counter()
 print('cpu per call us', (t1 - t0) / 2000 * 1e6, 'total incl gpu', (t2 - t0) / 2000 * 1e6)
-pr = cProfile.Profile(); pr.enable()
-for _ in range(2000): m(x)
-pr.disable(); torch.cuda.synchronize()
-pstats.Stats(pr).sort_stats('cumulative').print_stats(14)
+if not opt.brief:
+    import cProfile, pstats
+    pr = cProfile.Profile(); pr.enable()
+    for _ in range(2000): m(x)
+    pr.disable(); torch.cuda.synchronize()
+    pstats.Stats(pr).sort_stats('cumulative').print_stats(14)
 
 # ---- where the per-call time goes: the bare C-ABI call (two kernel launches) vs the Python around it
 from autosmoothquant_amd import _lib as L
 lib = L.lib()
 M, K, N = 32, 4096, 4096
 nbytes = lib.asq_linear_w8a8_workspace_bytes(M, N, K)
-ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-out = torch.empty(M, N, dtype=torch.float16, device=dev)
 st = torch.cuda.current_stream().cuda_stream
+ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+L.check(lib.asq_workspace_init(ws.data_ptr(), nbytes, st), "asq_workspace_init")   # (the workspace contract: a header-less buffer traps)
+out = torch.empty(M, N, dtype=torch.float16, device=dev)
 args = (x.data_ptr(), L.ASQ_F16, m.weight.data_ptr(), out.data_ptr(), M, N, K, L.ASQ_ACT_ROUND, 1.0, 1.0, None, None, ws.data_ptr(), nbytes, st)
 for _ in range(20): lib.asq_linear_w8a8_forward(*args)
 torch.cuda.synchronize()
@@ -40,17 +50,30 @@ t0 = time.perf_counter()
 for _ in range(2000): torch.empty((M, N), dtype=torch.float16, device=dev); torch.empty((nbytes,), dtype=torch.uint8, device=dev)
 t1 = time.perf_counter()
 print('two torch.empty us', (t1 - t0) / 2000 * 1e6)
-t0 = time.perf_counter()
-for _ in range(2000): ops.linear_w8a8_forward(x, m.weight, "per-tensor-round", 1.0, 1.0)
-t1 = time.perf_counter(); torch.cuda.synchronize()
-print('ops.linear_w8a8_forward us', (t1 - t0) / 2000 * 1e6)
+
+# ---- the ops that go through the general operand checks, same 2000-call pattern
+xq = torch.randint(-128, 128, (M, K), dtype=torch.int8, device=dev)
+qa = torch.randint(-128, 128, (32, 1, 128), dtype=torch.int8, device=dev)       # one decode step of 32 heads against 1024 cached keys
+kb = torch.randint(-128, 128, (32, 1024, 128), dtype=torch.int8, device=dev)
+for name, fn in (("ops.linear_w8a8_forward", lambda: ops.linear_w8a8_forward(x, m.weight, "per-tensor-round", 1.0, 1.0)),
+                 ("ops.linear_w8a8", lambda: ops.linear_w8a8(xq, m.weight, torch.float16, 1e-3)),
+                 ("ops.quantize_act", lambda: ops.quantize_act(x, "per-tensor-round")),
+                 ("ops.bmm_i8", lambda: ops.bmm_i8(qa, kb, torch.float32, 0.1))):
+    for _ in range(20): fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(2000): fn()
+    t1 = time.perf_counter(); torch.cuda.synchronize()
+    print(name, 'us', (t1 - t0) / 2000 * 1e6)
 
 # ---- A/B of the per-stream workspace cache (ops._forward_ws) in this process
 def _uncached(lib_, M_, N_, K_, dev_, stream_):
     n_ = lib_.asq_linear_w8a8_workspace_bytes(M_, N_, K_)
-    return torch.empty((n_,), dtype=torch.uint8, device=dev_), n_
+    buf = torch.empty((n_,), dtype=torch.uint8, device=dev_)
+    L.check(lib_.asq_workspace_init(buf.data_ptr(), n_, stream_), "asq_workspace_init")
+    return buf, n_
 cached = ops._forward_ws
-for name, fn in (("cached", cached), ("uncached", _uncached), ("cached", cached), ("uncached", _uncached)):
+for name, fn in (() if opt.brief else (("cached", cached), ("uncached", _uncached), ("cached", cached), ("uncached", _uncached))):
     ops._forward_ws = fn
     for _ in range(200): m(x)
     torch.cuda.synchronize()
