@@ -1,4 +1,4 @@
-"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h)."""
+"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h and include/asq_hip_attn.h)."""
 import ctypes
 import os
 import threading
@@ -101,6 +101,11 @@ SIGNATURES = {
     "asq_dq_add_layernorm_q": (_int, [_vp, _f32, _vp, _vp, _int, _vp, _vp, _f32, _vp, _i64, _i64, _vp]),
 }
 
+# include/asq_hip_attn.h: caller-side glue of int8 attention, a table of its own (SIGNATURES is closed with asq_hip.h at ASQ_VERSION 126; these are probed by presence)
+ATTN_SIGNATURES = {
+    "asq_rope_quantize_qkv": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _i64, _i64, _i64, _i64, _i64, _vp]),
+}
+
 
 def lib():
     """Load libasq_hip.so once.  Fails loudly: there is no fallback implementation."""
@@ -119,7 +124,7 @@ def lib():
                 # imported torch).  The host side above the C-ABI is torch plumbing anyway (ops.py).
                 import torch  # noqa: F401
                 h = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in SIGNATURES.items():
+                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()):
                     fn = getattr(h, name)  # AttributeError if the .so lacks a declared symbol
                     fn.restype, fn.argtypes = res, args
                 if h.asq_version() != ASQ_VERSION:   # a stale build: argument lists and the workspace contract may differ

@@ -9,7 +9,10 @@ q/k/v projections write them, a token-by-token KV cache holds them and o_proj re
 
 The reference stops at the two matmul modules and leaves the softmax between them to the caller (fp32 scores, eager softmax, a cast);
 here the first product carries it as its epilogue.  The state dict is the two scalar buffers ``qk_bmm.a`` and ``pv_bmm.a`` (host-pinned,
-following the module dtype, as in layers/nn/bmm.py)."""
+following the module dtype, as in layers/nn/bmm.py).
+
+What feeds it for a RoPE model (LLaMA, Mixtral, Baichuan-7B) is RopeQuantQKV: rotary embedding, the per-tensor int8 quantisers of q, k and v and the append to an
+Int8KVCache in one launch (ops.rope_quantize_qkv), straight from the q/k/v projections' [B, S, H, d] outputs into the operands of layout="bshd"."""
 import torch
 
 from ... import ops
@@ -96,3 +99,83 @@ class Int8Attention(torch.nn.Module):
             return ops.bmm_i8_kn(p, v, torch.int8, pv_alpha, heads=hkv).view(bsz, 1, hq, d)
         p = ops.bmm_i8_softmax_q8(q, k, qk_alpha, self.causal, b_group=r)
         return ops.bmm_i8_kn(p, v, torch.int8, pv_alpha, b_group=r, out_token=True, heads=hq)
+
+
+class Int8KVCache:
+    """A preallocated int8 KV cache in the token-major layout: k and v [B, Smax, Hkv, d] and the number of tokens held, `length` (one position for the whole batch).
+    Plain tensor bookkeeping, on any device: slot(S) -> the views k[:, length:length + S], v[...] that the next S tokens are written into (ValueError past
+    max_len), advance(S) -> length += S, view() -> k[:, :length], v[:, :length], reset() -> length = 0.  Nothing is copied; every view aliases the buffers.
+    With B == 1 view() is contiguous and is what Int8Attention(layout="bshd") takes as it is; see RopeQuantQKV for B > 1."""
+
+    def __init__(self, batch, max_len, kv_heads, head_dim, device=None):
+        self.k = torch.zeros((batch, max_len, kv_heads, head_dim), dtype=torch.int8, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.length = 0
+
+    @property
+    def max_len(self):
+        return self.k.shape[1]
+
+    def slot(self, S):
+        if S < 0 or self.length + S > self.max_len:
+            raise ValueError(f"Int8KVCache: {S} more tokens after {self.length} do not fit max_len {self.max_len}")
+        return self.k[:, self.length:self.length + S], self.v[:, self.length:self.length + S]
+
+    def advance(self, S):
+        self.slot(S)
+        self.length += S
+
+    def view(self):
+        return self.k[:, :self.length], self.v[:, :self.length]
+
+    def reset(self):
+        self.length = 0
+
+
+class RopeQuantQKV(torch.nn.Module):
+    """Rotary embedding of q and k, the static per-tensor int8 quantisers of q, k and v (x / scale in x's dtype, round, clamp) and the KV-cache append as ONE launch
+    (ops.rope_quantize_qkv): every byte is what ops.rope followed by ops.quantize_act(., "per-tensor-div", scale) gives.  The state dict is the three scalar buffers
+    ``q_scale``, ``k_scale`` and ``v_scale`` (host-pinned, following the module dtype, as ``a`` in layers/nn/bmm.py); the kernel receives fp32(scale.item()).
+
+    forward(q, k, v, cos, sin, pos=0, cache=None) -> (q8, k8, v8): q [B, S, Hq, d], k and v [B, S, Hkv, d] as the projections write them (dense or slices of a fused
+    q || k || v output), cos / sin [T, d/2] tables indexed by absolute position.  Without a cache the tokens sit at positions pos .. pos + S - 1 and k8 / v8 are fresh
+    dense tensors.  With an Int8KVCache the position is cache.length (`pos` is not used), k / v are written into cache.slot(S), the cache advances, and k8 / v8 are
+    cache.view(): all tokens so far, which Int8Attention(...)(q8, k8, v8, layout="bshd") consumes -- a prefill and every decode step alike.
+
+    Limit: Int8Attention's bshd path needs contiguous K / V, which a cache view is for B == 1 (the single-sequence decode step attention.py documents).  For B > 1 the
+    launch still appends correctly (the cache's batch pitch goes to the kernel), but consuming the view without a copy needs a batch pitch on the token-major b
+    operand of asq_bmm_i8, which it does not have yet: make the views contiguous first."""
+
+    _SCALES = ("q_scale", "k_scale", "v_scale")
+
+    def __init__(self, q_scale=1.0, k_scale=1.0, v_scale=1.0):
+        super().__init__()
+        for name, s in zip(self._SCALES, (q_scale, k_scale, v_scale)):
+            self.register_buffer(name, s.detach().clone() if torch.is_tensor(s) else torch.tensor(s))
+        self._pin()
+
+    def _pin(self):
+        for name in self._SCALES:
+            t = self._buffers.get(name)
+            if t is not None and t.device.type != "cpu":
+                self._buffers[name] = t.detach().to("cpu")
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        self._pin()
+        return self
+
+    def _scales(self):
+        self._pin()   # a device tensor assigned from outside: one copy, then host reads are free
+        return tuple(self._buffers[name].item() for name in self._SCALES)
+
+    def forward(self, q, k, v, cos, sin, pos=0, cache=None):
+        qs, ks, vs = self._scales()
+        if cache is None:
+            return ops.rope_quantize_qkv(q, k, v, cos, sin, qs, ks, vs, pos=pos)
+        S = q.shape[1] if torch.is_tensor(q) and q.dim() == 4 else 0
+        k_out, v_out = cache.slot(S)
+        q8, _, _ = ops.rope_quantize_qkv(q, k, v, cos, sin, qs, ks, vs, pos=cache.length, k_out=k_out, v_out=v_out)
+        cache.advance(S)
+        k8, v8 = cache.view()
+        return q8, k8, v8

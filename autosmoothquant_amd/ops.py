@@ -690,24 +690,86 @@ def silu_mul(gate, up, fast=None):
     return out
 
 
+def _hip(t, name):
+    """t is a HIP tensor (it may be a strided view: _dev's contiguity check does not apply)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a HIP (cuda:N) tensor; there is no CPU fallback")
+    return t
+
+
+def _bshd_pitch(x, name):
+    """x [B, S, H, D] with H * D contiguous and ONE pitch between consecutive (b, s) rows -- dense, or a slice of a fused q || k || v output (strides
+    (S * ld, ld, D, 1) with ld >= H * D) -> ld in elements"""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _DT or x.dim() != 4:
+        raise ValueError(f"{name} must be a [B, S, H, D] float tensor")
+    B, S, H, D = x.shape
+    st = x.stride()
+    ld = st[1] if S > 1 else (st[0] if B > 1 else H * D)
+    if not (st[3] == 1 and st[2] == D and ld >= H * D and (B == 1 or S == 1 or st[0] == S * ld)) or (S == 1 and B > 1 and st[0] < H * D):
+        raise ValueError(f"{name} must be [B, S, H, D] with H * D contiguous and one row pitch (a projection output or a slice of a fused one)")
+    return ld
+
+
 def rope(x, cos, sin, out=None):
     """Rotary embedding of x [B, S, H, D] in one pass (asq_rope): x is a q / k projection's output viewed per head -- dense, or a slice of a fused q || k || v output
     (strides (S * ld, ld, D, 1) with ld >= H * D); cos / sin [S, D/2] of x's dtype, positions 0 .. S-1, rotate_half convention.  Returns a DENSE [B, S, H, D] tensor
     (out=x rotates a dense x in place).  fp16: bit-identical to the torch composition addcmul(x1 * cos, x2, sin, value=-1) / addcmul(x2 * cos, x1, sin) it replaces
     (harness._rope_torch); bf16: the same operations at fp32 width."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:   # (x may be a strided slice: _dev's contiguity check does not apply)
-        raise RuntimeError("x must be a HIP (cuda:N) tensor; there is no CPU fallback")
-    if x.dtype not in _DT or x.dim() != 4:
-        raise ValueError("x must be a [B, S, H, D] float tensor")
+    ld = _bshd_pitch(_hip(x, "x"), "x")
     B, S, H, D = x.shape
-    st = x.stride()
-    ld = st[1] if S > 1 else (st[0] if B > 1 else H * D)
-    if not (st[3] == 1 and st[2] == D and ld >= H * D and (B == 1 or S == 1 or st[0] == S * ld)) or (S == 1 and B > 1 and st[0] < H * D):
-        raise ValueError("x must be [B, S, H, D] with H * D contiguous and one row pitch (a projection output or a slice of a fused one)")
     _operand(cos, "cos", x.dtype, S * (D // 2)), _operand(sin, "sin", x.dtype, S * (D // 2))   # ([S, D/2] tables of x's dtype)
     out = _out(out, (B, S, H, D), x.dtype, x.device)
     _launch("asq_rope", _same_device(x, cos, sin), x.data_ptr(), ld, out.data_ptr(), _DT[x.dtype], cos.data_ptr(), sin.data_ptr(), B, S, H, D, _stream(x))
     return out
+
+
+def _kv_slot(t, name, shape):
+    """k_out / v_out of rope_quantize_qkv: an int8 [B, S, Hkv, D] view with strides (pitch, Hkv * D, D, 1), e.g. cache[:, p:p + S] -> the batch pitch (0: one sequence)"""
+    B, S, H, D = shape
+    st = t.stride() if isinstance(t, torch.Tensor) else None
+    if st is None or t.dtype != torch.int8 or tuple(t.shape) != shape or st[3] != 1 or st[2] != D or (S > 1 and st[1] != H * D) or (B > 1 and st[0] < S * H * D):
+        raise ValueError(f"{name} must be an int8 {list(shape)} view with strides (pitch, Hkv * D, D, 1) and pitch >= S * Hkv * D, got "
+                         f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))} with strides {st}")
+    return st[0] if B > 1 else 0
+
+
+def rope_quantize_qkv(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos=0, k_out=None, v_out=None):
+    """Rotary embedding of q and k at positions pos .. pos + S - 1, per-tensor int8 quantisation of q, k and v, and the write of k / v into a KV cache, in ONE launch
+    (asq_rope_quantize_qkv) -> (q8, k8, v8).  q [B, S, Hq, D], k and v [B, S, Hkv, D] of one float dtype, each dense or a slice of a fused q || k || v output (rope's
+    stride rule, one pitch per tensor); cos / sin contiguous [T, D/2] of that dtype with T >= pos + S.  q8 is a fresh dense int8 [B, S, Hq, D].  k_out / v_out (both or
+    neither): int8 [B, S, Hkv, D] views with strides (pitch, Hkv * D, D, 1) and one common pitch, e.g. cache_k[:, p:p + S] of a [B, Smax, Hkv, D] cache -- written and
+    returned as k8 / v8, nothing outside them is touched; otherwise fresh dense tensors.
+    Every byte equals rope(x, cos[pos:pos + S], sin[pos:pos + S]) followed by quantize_act(., "per-tensor-div", scale) (v: the quantiser alone), by construction.
+    Shapes and strides are checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
+    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or tuple(k.shape) != (B, S, Hkv, D):
+        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
+    pos = int(pos)
+    if (not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or D % 2 or cos.dim() != 2 or sin.shape != cos.shape or cos.shape[1] != D // 2 or pos < 0
+            or cos.shape[0] < pos + S):
+        raise ValueError(f"cos / sin must be [T, {D // 2}] tables with T >= pos + S = {pos + S} (pos {pos}), got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
+    T = cos.shape[0]
+    if (k_out is None) != (v_out is None):
+        raise ValueError("k_out and v_out come together")
+    kvb = 0
+    if k_out is not None:
+        kvb, vb = _kv_slot(k_out, "k_out", (B, S, Hkv, D)), _kv_slot(v_out, "v_out", (B, S, Hkv, D))
+        if kvb != vb:
+            raise ValueError(f"k_out and v_out must have one common batch pitch, got {kvb} and {vb}")
+    _hip(q, "q"), _hip(k, "k"), _hip(v, "v")
+    _operand(cos, "cos", q.dtype, T * (D // 2)), _operand(sin, "sin", q.dtype, T * (D // 2))
+    if k_out is None:
+        k8, v8 = torch.empty((B, S, Hkv, D), dtype=torch.int8, device=q.device), torch.empty((B, S, Hkv, D), dtype=torch.int8, device=q.device)
+    else:
+        k8, v8 = _hip(k_out, "k_out"), _hip(v_out, "v_out")
+        _bump_version(k8), _bump_version(v8)
+    dev = _same_device(q, k, v, cos, sin, k8, v8)
+    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
+    _launch("asq_rope_quantize_qkv", dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[q.dtype], cos.data_ptr(), sin.data_ptr(), T, pos,
+            q8.data_ptr(), k8.data_ptr(), v8.data_ptr(), kvb, float(q_scale), float(k_scale), float(v_scale), B, S, Hq, Hkv, D, _stream(q))
+    return q8, k8, v8
 
 
 def silu_mul_quantize_fp8(gate, up, fast=None):
