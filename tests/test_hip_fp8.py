@@ -1,7 +1,9 @@
 """GPU (-m gpu): the FP8 (e4m3fn / e5m2) linear path through the C-ABI.
 Quantiser outputs are compared BIT-EXACTLY with the oracle (pinned to the reference by G5);
 linear outputs within rtol 1e-3 / atol 1e-3*max|out| (the reference dequantises and calls
-F.linear; summation order unspecified -> tolerance, as SURVEY 8c states)."""
+F.linear; summation order unspecified -> tolerance, as SURVEY 8c states).
+The tolerance is relative to the largest output of the matrix: on operands where every fp32 partial sum is exact in any order, tests/test_hip_fp8_exact.py
+compares the same entries (e4m3 and e5m2, grouped, MX; every kernel form) bit for bit on every element."""
 import os
 
 import numpy as np
