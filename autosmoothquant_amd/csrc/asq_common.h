@@ -60,6 +60,18 @@ int asq_try_fused_forward(const void *x, int x_dtype, const int8_t *w, void *out
 
 static inline size_t asq_dtype_size(int dt) { return dt == ASQ_F32 ? 4 : 2; }
 
+// The runtime dtype code (checked by the entry's own ASQ_REQUIRE) as a compile-time constant: returns f(std::integral_constant<int, dt>{}).
+template <class F> static inline auto asq_dispatch_dt(int dt, F &&f)
+{
+    switch (dt) {
+    case ASQ_F32: return f(std::integral_constant<int, ASQ_F32>{});
+    case ASQ_F16: return f(std::integral_constant<int, ASQ_F16>{});
+    default: return f(std::integral_constant<int, ASQ_BF16>{});
+    }
+}
+// the same for a two-way choice: f(std::true_type{}) or f(std::false_type{})
+template <class F> static inline auto asq_dispatch_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
 // ---------------------------------------------------------------------------------
 // device: logical-dtype conversions (one IEEE rounding, as ATen's CPU kernels do)
 // ---------------------------------------------------------------------------------
@@ -154,6 +166,12 @@ __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(v2us, a), __builtin_bit_cast(v2us, b)));
 }
 __device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t wave_umax32(uint32_t m)   // the maximum over the 64 lanes of a wave, in every lane
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = umax32(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    return m;
+}
 __device__ __forceinline__ uint32_t absbits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
 
 // one 16-byte vector of DT elements as floats (4 x fp32 or 8 x fp16 / bf16)
@@ -189,12 +207,25 @@ template <int DT> struct AbsMax {  // running |x| maximum of raw DT vectors
     }
 };
 
+// A wave's own 16-byte non-temporal loads, issued without waiting (the one-wave-per-row quantisers, asq_quant.hip / asq_fp8.hip).  hipcc does not count asm memory
+// operations, so the caller waits by hand: wait_vm<N>() before the first use, pin_vgprs() to keep the uses of the registers below that wait.
+__device__ __forceinline__ void load16_nt_async(v4i &dst, const void *p)
+{
+    asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(dst) : "v"(p) : "memory");
+}
+__device__ __forceinline__ void pin_vgprs(v4i &x) { asm volatile("" : "+v"(x)); }   // (uses of x stay below this point)
+template <int N> __device__ __forceinline__ void wait_vm()   // at most N vector memory operations still in flight (they retire in issue order)
+{
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 // block-wide maximum of fp32 |x| bit patterns (256 threads) -> float (NaN if any NaN)
 __device__ __forceinline__ float block_absmax_256(uint32_t m, float *red_f)
 {
     uint32_t *red = (uint32_t *)red_f;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = umax32(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    for (int off = 32; off > 0; off >>= 1) m = umax32(m, (uint32_t)__shfl_xor((int)m, off, 64));   // (not wave_umax32: through the call hipcc orders the LDS store's address differently)
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) red[wave] = m;
     __syncthreads();

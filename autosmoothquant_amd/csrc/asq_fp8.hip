@@ -70,6 +70,16 @@ template <int DT, class Q> __device__ __forceinline__ void f8_quant_vec(const v4
     }
 }
 
+// the codes of one 16-byte input vector, idx counted in such vectors: 4 (fp32) or 8 bytes
+template <int DT> __device__ __forceinline__ void f8_store_vec(uint8_t *out, int64_t idx, const uint32_t (&o)[2])
+{
+    if constexpr (DT == ASQ_F32) *(uint32_t *)(out + idx * 4) = o[0];
+    else *(uint2 *)(out + idx * 8) = make_uint2(o[0], o[1]);
+}
+
+// rowabsmax.div(finfo.max) in x's dtype, then .to(float32) (quantization.py:183); per-tensor: amax / finfo.max in x's dtype (:162)
+template <int DT> __device__ __forceinline__ float f8_row_scale(float m) { return ElemT<DT>::round(m / 448.0f); }
+
 // per-token: one block per row, two passes over the row (second pass hits L1/L2); any K
 template <int DT>
 __global__ void __launch_bounds__(256) fp8_quant_per_token(const void *__restrict__ xv, uint8_t *__restrict__ xq, float *__restrict__ scale, int64_t K,
@@ -91,15 +101,14 @@ __global__ void __launch_bounds__(256) fp8_quant_per_token(const void *__restric
         for (int64_t k = threadIdx.x; k < K; k += 256) mb = umax32(mb, absbits(ElemT<DT>::load(xrow[k])));
     }
     const float m = block_absmax_256(mb, red);
-    const float s = ElemT<DT>::round(m / 448.0f);  // rowabsmax.div(finfo.max) in x's dtype, then .to(float32)
+    const float s = f8_row_scale<DT>(m);
     if (threadIdx.x == 0) scale[row] = s;
     auto emit = [&](auto q) {
         if (vec) {
             for (int64_t i = threadIdx.x; i < K / VEC; i += 256) {
                 uint32_t o[2];
                 f8_quant_vec<DT>(*(const v4i *)((const char *)xrow + i * 16), q, o);
-                if constexpr (DT == ASQ_F32) *(uint32_t *)(orow + i * 4) = o[0];
-                else *(uint2 *)(orow + i * 8) = make_uint2(o[0], o[1]);
+                f8_store_vec<DT>(orow, i, o);
             }
         } else {
             for (int64_t k = threadIdx.x; k < K; k += 256) orow[k] = (uint8_t)f8_one<false>(q(ElemT<DT>::load(xrow[k])));
@@ -112,9 +121,8 @@ __global__ void __launch_bounds__(256) fp8_quant_per_token(const void *__restric
 
 // ---- one WAVE per row (round 6; the int8 side's quant_rows_wave, asq_quant.hip): the block kernel above reads every row twice behind two block-wide reductions -- at
 // Mixtral's w2 input (8192 x 14336 fp16) that is the slowest non-GEMM launch of the fp8 expert step.  Here a wave owns a row: NV non-temporal 16-byte loads per lane in
-// flight (inline asm, waits counted by hand: hipcc does not count asm memory operations), the maximum a wave butterfly, the row quantised from registers -- one HBM read,
+// flight (asq_common.h load16_nt_async, the wait by hand), the maximum a wave butterfly, the row quantised from registers -- one HBM read,
 // no LDS, no barrier, 4 rows per block.  Same arithmetic, same functors as fp8_quant_per_token: bit-identical outputs.  Rows of up to 64 * 28 vectors (14336 fp16 elements).
-__device__ __forceinline__ void f8_load16_nt_async(v4i &dst, const void *p) { asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(dst) : "v"(p) : "memory"); }
 template <int DT, int NV>
 __global__ void __launch_bounds__(256) fp8_quant_rows_wave(const void *__restrict__ xv, uint8_t *__restrict__ xq, float *__restrict__ scale, int M, int K)
 {
@@ -128,20 +136,17 @@ __global__ void __launch_bounds__(256) fp8_quant_rows_wave(const void *__restric
 #pragma unroll
     for (int i = 0; i < NV; ++i) {   // a lane past the end of the row re-reads the row's last vector (a duplicate changes no maximum; its store is skipped)
         const int idx = i * 64 + lane;
-        f8_load16_nt_async(v[i], xrow + (int64_t)(idx < nvec ? idx : nvec - 1) * 16);
+        load16_nt_async(v[i], xrow + (int64_t)(idx < nvec ? idx : nvec - 1) * 16);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     AbsMax<DT> am;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        asm volatile("" : "+v"(v[i]));   // (uses of v[i] stay below the wait)
+        pin_vgprs(v[i]);
         am.add(v[i]);
     }
-    uint32_t mb = am.f32bits();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mb = umax32(mb, (uint32_t)__shfl_xor((int)mb, off, 64));
-    const float m = __uint_as_float(mb);
-    const float s = ElemT<DT>::round(m / 448.0f);  // rowabsmax.div(finfo.max) in x's dtype, then .to(float32)
+    const float m = __uint_as_float(wave_umax32(am.f32bits()));
+    const float s = f8_row_scale<DT>(m);
     if (lane == 0) scale[row] = s;
     uint8_t *orow = xq + row * (int64_t)K;
     auto emit = [&](auto q) {
@@ -150,10 +155,7 @@ __global__ void __launch_bounds__(256) fp8_quant_rows_wave(const void *__restric
             const int idx = i * 64 + lane;
             uint32_t o[2];
             f8_quant_vec<DT>(v[i], q, o);
-            if (idx < nvec) {
-                if constexpr (DT == ASQ_F32) *(uint32_t *)(orow + (int64_t)idx * 4) = o[0];
-                else *(uint2 *)(orow + (int64_t)idx * 8) = make_uint2(o[0], o[1]);
-            }
+            if (idx < nvec) f8_store_vec<DT>(orow, idx, o);
         }
     };
     const RowDivisor d(s, m);
@@ -218,7 +220,7 @@ __global__ void __launch_bounds__(256) fp8_quant_per_tensor(const void *__restri
     float s = host_scale, amax = __builtin_inff();  // static mode: nothing is known about x -> plain division
     if (amax_bits) {
         amax = __uint_as_float(*amax_bits);
-        s = ElemT<DT>::round(amax / 448.0f);  // amax / finfo.max in x's dtype
+        s = f8_row_scale<DT>(amax);
     }
     if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) *scale_out = s;
     const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -227,8 +229,7 @@ __global__ void __launch_bounds__(256) fp8_quant_per_tensor(const void *__restri
             for (int64_t i = t0; i < n / VEC; i += stride) {
                 uint32_t o[2];
                 f8_quant_vec<DT>(*((const v4i *)xv + i), q, o);
-                if constexpr (DT == ASQ_F32) *((uint32_t *)xq + i) = o[0];
-                else *((uint2 *)xq + i) = make_uint2(o[0], o[1]);
+                f8_store_vec<DT>(xq, i, o);
             }
             for (int64_t k = (n / VEC) * VEC + t0; k < n; k += stride) xq[k] = (uint8_t)f8_one<false>(q(ElemT<DT>::load(((const T *)xv)[k])));
         } else {
@@ -238,6 +239,13 @@ __global__ void __launch_bounds__(256) fp8_quant_per_tensor(const void *__restri
     const RowDivisor d(s, amax);
     if (d.fast) emit(F8DivFast<DT>{QRowFast{d.s, d.y}});
     else emit(F8Div<DT>{s});
+}
+
+// grid of the flat (grid-stride) kernels: a thread per 8 elements, at most 4096 blocks
+static inline unsigned f8_flat_blocks(int64_t n)
+{
+    const int64_t blocks = (n / 8 + 255) / 256;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
 }
 
 template <int DT>
@@ -252,8 +260,7 @@ int fp8_quantize_dt(const void *x, int mode, float static_scale, uint8_t *xq, fl
         return asq_after_launch(s, "asq_quantize_act_fp8(per-token)");
     }
     const bool vec = ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)xq) & 7) == 0);
-    int64_t blocks = (n / 8 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
+    const dim3 blocks(f8_flat_blocks(n));
     if (mode == ASQ_FP8_PER_TENSOR) {
         unsigned *amax = (unsigned *)(scale_out + 1);  // scale_out[0] = scale, scale_out[1] = scratch word for the absmax
         hipError_t e = hipMemsetAsync(amax, 0, 4, s);
@@ -261,33 +268,24 @@ int fp8_quantize_dt(const void *x, int mode, float static_scale, uint8_t *xq, fl
             asq_set_error("asq_quantize_act_fp8: hipMemsetAsync: %s", hipGetErrorString(e));
             return (int)e;
         }
-        hipLaunchKernelGGL((fp8_absmax<DT>), dim3((unsigned)blocks), dim3(256), 0, s, x, n, vec, amax);
-        hipLaunchKernelGGL((fp8_quant_per_tensor<DT>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, n, vec, (const unsigned *)amax, 0.0f, scale_out);
+        hipLaunchKernelGGL((fp8_absmax<DT>), blocks, dim3(256), 0, s, x, n, vec, amax);
+        hipLaunchKernelGGL((fp8_quant_per_tensor<DT>), blocks, dim3(256), 0, s, x, xq, n, vec, (const unsigned *)amax, 0.0f, scale_out);
     } else {
-        hipLaunchKernelGGL((fp8_quant_per_tensor<DT>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, n, vec, (const unsigned *)nullptr, static_scale,
+        hipLaunchKernelGGL((fp8_quant_per_tensor<DT>), blocks, dim3(256), 0, s, x, xq, n, vec, (const unsigned *)nullptr, static_scale,
                            scale_out);
     }
     return asq_after_launch(s, "asq_quantize_act_fp8(per-tensor)");
 }
 
-template <int DT, class MMA>
-int launch_fp8_linear(const int8_t *xq, const int8_t *w, void *out, int64_t M, int64_t N, int64_t K, const float *a_scale_dev, bool a_per_token,
-                      float a_scale_host, float w_scale, const float *bias, bool vec_ok, hipStream_t s)
+// The epilogue of the three fp8 linears (asq_linear_fp8, _grouped, asq_linear_mxfp8's tiled form), its bias form and its vector test chosen once: returns f(epi)
+template <int DT, class MMA, class F>
+static int with_fp8_epi(void *out, int64_t N, const float *a_scale_dev, bool a_per_token, float a_scale_host, float w_scale, const float *w_scale_group,
+                        const float *bias, F &&f)
 {
-    if (bias)
-        return launch_gemm(xq, w, M, N, K, EpiFp8<DT, true, MMA>{out, N, a_scale_dev, bias, nullptr, a_scale_host, w_scale, a_per_token, vec_ok}, s, "asq_linear_fp8");
-    return launch_gemm(xq, w, M, N, K, EpiFp8<DT, false, MMA>{out, N, a_scale_dev, bias, nullptr, a_scale_host, w_scale, a_per_token, vec_ok}, s, "asq_linear_fp8");
-}
-
-template <int DT>
-int launch_fp8_grouped(const int8_t *xq, const int8_t *w, void *out, int64_t M, int64_t N, int64_t K, const float *a_scale, const float *w_scale_group,
-                       const float *bias, bool vec_ok, const int *goffs, int ngroups, hipStream_t s)
-{
-    if (bias)
-        return launch_gemm(xq, w, M, N, K, EpiFp8<DT, true, MmaFp8>{out, N, a_scale, bias, w_scale_group, 1.0f, 1.0f, true, vec_ok}, s, "asq_linear_fp8_grouped",
-                           nullptr, 0, goffs, ngroups);
-    return launch_gemm(xq, w, M, N, K, EpiFp8<DT, false, MmaFp8>{out, N, a_scale, bias, w_scale_group, 1.0f, 1.0f, true, vec_ok}, s, "asq_linear_fp8_grouped",
-                       nullptr, 0, goffs, ngroups);
+    const bool vec_ok = epi_vec_ok(out, DT, N, bias);
+    return asq_dispatch_bool(bias != nullptr, [&](auto has_bias) {
+        return f(EpiFp8<DT, decltype(has_bias)::value, MMA>{out, N, a_scale_dev, bias, w_scale_group, a_scale_host, w_scale, a_per_token, vec_ok});
+    });
 }
 
 // ---------------------------------------------------------------------------------
@@ -341,7 +339,7 @@ __global__ void __launch_bounds__(256) silu_mul_quant_fp8_cached(const void *__r
     }
     if constexpr (H) amax = __float_as_uint(ElemT<DT>::load((uint16_t)umax32(amax & 0xFFFFu, amax >> 16)));  // widening keeps the order, NaN stays NaN
     const float m = block_absmax_256(amax, red);
-    const float s = ElemT<DT>::round(m / 448.0f);  // rowabsmax.div(finfo.max) in the activation dtype, then .to(float32)
+    const float s = f8_row_scale<DT>(m);  // (in the activation dtype)
     if (threadIdx.x == 0) scale[row] = s;
     uint8_t *orow = xq + row * (int64_t)K;
     auto emit = [&](auto q) {
@@ -361,8 +359,9 @@ __global__ void __launch_bounds__(256) silu_mul_quant_fp8_cached(const void *__r
                         r[j + 1] = q(a[i][j + 1]);
                     }
                 }
-                if constexpr (DT == ASQ_F32) *(uint32_t *)(orow + (int64_t)idx * 4) = f8_pack4<false>(r[0], r[1], r[2], r[3]);
-                else *(uint2 *)(orow + (int64_t)idx * 8) = make_uint2(f8_pack4<false>(r[0], r[1], r[2], r[3]), f8_pack4<false>(r[4], r[5], r[6], r[7]));
+                uint32_t o[2] = {f8_pack4<false>(r[0], r[1], r[2], r[3]), 0};
+                if constexpr (DT != ASQ_F32) o[1] = f8_pack4<false>(r[4], r[5], r[6], r[7]);
+                f8_store_vec<DT>(orow, idx, o);
             }
         }
     };
@@ -396,8 +395,7 @@ template <int DT> __global__ void __launch_bounds__(256) cast_e5m2_kernel(const 
         for (int64_t i = t0; i < n / VEC; i += stride) {
             uint32_t o[2];
             f8_quant_vec<DT>(*((const v4i *)xv + i), q, o);
-            if constexpr (DT == ASQ_F32) *((uint32_t *)xq + i) = o[0];
-            else *((uint2 *)xq + i) = make_uint2(o[0], o[1]);
+            f8_store_vec<DT>(xq, i, o);
         }
         for (int64_t k = (n / VEC) * VEC + t0; k < n; k += stride) xq[k] = (uint8_t)f8_one<true>(q(ElemT<DT>::load(((const T *)xv)[k])));
     } else {
@@ -495,30 +493,20 @@ __global__ void __launch_bounds__(256) mx_gemm_e4m3(const uint8_t *__restrict__ 
         }
 }
 
-template <int DT, bool HAS_BIAS>
-static int launch_mx_tiled_one(const int8_t *xq, const uint8_t *xs, const int8_t *wq, const uint8_t *ws, void *out, int64_t M, int64_t N, int64_t K, const float *bias,
-                               hipStream_t s)
-{
-    using Epi = EpiFp8<DT, HAS_BIAS, MmaFp8>;
-    const size_t vbytes = DT == ASQ_F32 ? 16 : 8;
-    const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)bias) & 15) == 0);
-    Epi epi{out, N, nullptr, bias, nullptr, 1.0f, 1.0f, false, vec_ok};  // unit epilogue scales: the block scales are inside the product
-    const int64_t tm = (M + 127) / 128, tn = (N + 127) / 128;
-    ASQ_REQUIRE(tm * tn < (1ll << 24), ASQ_ERR_DIM, "asq_linear_mxfp8: too many tiles");
-    const int rc = launch_lds("asq_linear_mxfp8", gemm_i8_p8q<Epi, true>, P8Q_MX_LDS_BYTES, P8Q_MX_LDS_BYTES, tm * tn, 512, s, xq, wq, M, N, K, (int)tm, (int)tn, 1, epi, xs, ws);
-    return rc != ASQ_OK ? rc : asq_after_launch(s, "asq_linear_mxfp8");
-}
 static int launch_mx_tiled(int out_dtype, const int8_t *xq, const uint8_t *xs, const int8_t *wq, const uint8_t *ws, void *out, int64_t M, int64_t N, int64_t K,
                            const float *bias, hipStream_t s)
 {
     if (((((uintptr_t)xs) | ((uintptr_t)ws)) & 15) != 0) return ASQ_ERR_ALIGN;
-#define ASQ_MX_CASE(DT) (bias ? launch_mx_tiled_one<DT, true>(xq, xs, wq, ws, out, M, N, K, bias, s) : launch_mx_tiled_one<DT, false>(xq, xs, wq, ws, out, M, N, K, bias, s))
-    switch (out_dtype) {
-    case ASQ_F32: return ASQ_MX_CASE(ASQ_F32);
-    case ASQ_F16: return ASQ_MX_CASE(ASQ_F16);
-    default: return ASQ_MX_CASE(ASQ_BF16);
-    }
-#undef ASQ_MX_CASE
+    const int64_t tm = (M + 127) / 128, tn = (N + 127) / 128;
+    ASQ_REQUIRE(tm * tn < (1ll << 24), ASQ_ERR_DIM, "asq_linear_mxfp8: too many tiles");
+    return asq_dispatch_dt(out_dtype, [&](auto dt) {
+        // unit epilogue scales: the block scales are inside the product
+        return with_fp8_epi<decltype(dt)::value, MmaFp8>(out, N, nullptr, false, 1.0f, 1.0f, nullptr, bias, [&](auto epi) {
+            const int rc = launch_lds("asq_linear_mxfp8", gemm_i8_p8q<decltype(epi), true>, P8Q_MX_LDS_BYTES, P8Q_MX_LDS_BYTES, tm * tn, 512, s, xq, wq, M, N, K, (int)tm,
+                                      (int)tn, 1, epi, xs, ws);
+            return rc != ASQ_OK ? rc : asq_after_launch(s, "asq_linear_mxfp8");
+        });
+    });
 }
 
 }  // namespace asq
@@ -548,11 +536,7 @@ extern "C" int asq_quantize_act_fp8(const void *x, int x_dtype, int mode, float 
     }
     ASQ_REQUIRE(x != nullptr && xq != nullptr, ASQ_ERR_NULL, "asq_quantize_act_fp8: NULL x / xq");
     ASQ_REQUIRE(((uintptr_t)x % asq_dtype_size(x_dtype)) == 0, ASQ_ERR_ALIGN, "asq_quantize_act_fp8: x misaligned");
-    switch (x_dtype) {
-    case ASQ_F32: return fp8_quantize_dt<ASQ_F32>(x, mode, static_scale, xq, scale_out, M, K, s);
-    case ASQ_F16: return fp8_quantize_dt<ASQ_F16>(x, mode, static_scale, xq, scale_out, M, K, s);
-    default: return fp8_quantize_dt<ASQ_BF16>(x, mode, static_scale, xq, scale_out, M, K, s);
-    }
+    return asq_dispatch_dt(x_dtype, [&](auto dt) { return fp8_quantize_dt<decltype(dt)::value>(x, mode, static_scale, xq, scale_out, M, K, s); });
 }
 
 extern "C" int asq_silu_mul_quantize_fp8(const void *gate, const void *up, int x_dtype, int flags, uint8_t *xq, float *scale, int64_t M, int64_t K, void *stream)
@@ -569,13 +553,9 @@ extern "C" int asq_silu_mul_quantize_fp8(const void *gate, const void *up, int x
                 "asq_silu_mul_quantize_fp8: gate / up must be 16-B aligned, xq 8-B, scale 4-B");
     hipStream_t s = (hipStream_t)stream;
     const bool fast = (flags & ASQ_SILU_FAST) != 0;
-#define ASQ_SM8_DT(DT_) (fast ? launch_silu_mul_quant_fp8<DT_, true>(gate, up, xq, scale, M, K, s) : launch_silu_mul_quant_fp8<DT_, false>(gate, up, xq, scale, M, K, s))
-    switch (x_dtype) {
-    case ASQ_F32: return ASQ_SM8_DT(ASQ_F32);
-    case ASQ_F16: return ASQ_SM8_DT(ASQ_F16);
-    default: return ASQ_SM8_DT(ASQ_BF16);
-    }
-#undef ASQ_SM8_DT
+    return asq_dispatch_dt(x_dtype, [&](auto dt) {
+        return asq_dispatch_bool(fast, [&](auto fs) { return launch_silu_mul_quant_fp8<decltype(dt)::value, decltype(fs)::value>(gate, up, xq, scale, M, K, s); });
+    });
 }
 
 extern "C" int asq_cast_e5m2(const void *x, int x_dtype, uint8_t *xq, int64_t n, void *stream)
@@ -586,13 +566,7 @@ extern "C" int asq_cast_e5m2(const void *x, int x_dtype, uint8_t *xq, int64_t n,
     ASQ_REQUIRE(x != nullptr && xq != nullptr, ASQ_ERR_NULL, "asq_cast_e5m2: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
     const bool vec = ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)xq) & 7) == 0);
-    int64_t blocks = (n / 8 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-    switch (x_dtype) {
-    case ASQ_F32: hipLaunchKernelGGL((cast_e5m2_kernel<ASQ_F32>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, n, vec); break;
-    case ASQ_F16: hipLaunchKernelGGL((cast_e5m2_kernel<ASQ_F16>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, n, vec); break;
-    default: hipLaunchKernelGGL((cast_e5m2_kernel<ASQ_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, n, vec); break;
-    }
+    asq_dispatch_dt(x_dtype, [&](auto dt) { hipLaunchKernelGGL((cast_e5m2_kernel<decltype(dt)::value>), dim3(f8_flat_blocks(n)), dim3(256), 0, s, x, xq, n, vec); });
     return asq_after_launch(s, "asq_cast_e5m2");
 }
 
@@ -606,24 +580,15 @@ extern "C" int asq_linear_fp8(const uint8_t *xq, const uint8_t *w, int fp8_forma
     ASQ_REQUIRE(fp8_format == ASQ_FP8_E4M3 || fp8_format == ASQ_FP8_E5M2, ASQ_ERR_DTYPE, "asq_linear_fp8: bad fp8_format %d", fp8_format);
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(out_dtype)) == 0 && ((((uintptr_t)a_scale_dev | (uintptr_t)bias) & 3) == 0), ASQ_ERR_ALIGN,
                 "asq_linear_fp8: misaligned pointer");
-    const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
-    const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)bias) & 15) == 0);
     hipStream_t s = (hipStream_t)stream;
     const int8_t *xa = (const int8_t *)xq, *wa = (const int8_t *)w;
-#define ASQ_F8L(DT_, MMA_) launch_fp8_linear<DT_, MMA_>(xa, wa, out, M, N, K, a_scale_dev, a_per_token != 0, a_scale_host, w_scale, bias, vec_ok, s)
-    if (fp8_format == ASQ_FP8_E4M3) {
-        switch (out_dtype) {
-        case ASQ_F32: return ASQ_F8L(ASQ_F32, MmaFp8);
-        case ASQ_F16: return ASQ_F8L(ASQ_F16, MmaFp8);
-        default: return ASQ_F8L(ASQ_BF16, MmaFp8);
-        }
-    }
-    switch (out_dtype) {
-    case ASQ_F32: return ASQ_F8L(ASQ_F32, MmaBf8);
-    case ASQ_F16: return ASQ_F8L(ASQ_F16, MmaBf8);
-    default: return ASQ_F8L(ASQ_BF16, MmaBf8);
-    }
-#undef ASQ_F8L
+    return asq_dispatch_bool(fp8_format == ASQ_FP8_E4M3, [&](auto e4m3) {
+        using MMA = std::conditional_t<decltype(e4m3)::value, MmaFp8, MmaBf8>;
+        return asq_dispatch_dt(out_dtype, [&](auto dt) {
+            return with_fp8_epi<decltype(dt)::value, MMA>(out, N, a_scale_dev, a_per_token != 0, a_scale_host, w_scale, nullptr, bias,
+                                                          [&](auto epi) { return launch_gemm(xa, wa, M, N, K, epi, s, "asq_linear_fp8"); });
+        });
+    });
 }
 
 extern "C" int asq_linear_fp8_grouped(const uint8_t *xq, const uint8_t *w, void *out, int out_dtype, const int32_t *group_offsets, int ngroups, int64_t M,
@@ -638,15 +603,13 @@ extern "C" int asq_linear_fp8_grouped(const uint8_t *xq, const uint8_t *w, void 
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(out_dtype)) == 0 &&
                     ((((uintptr_t)a_scale | (uintptr_t)w_scale_group | (uintptr_t)bias | (uintptr_t)group_offsets) & 3) == 0),
                 ASQ_ERR_ALIGN, "asq_linear_fp8_grouped: misaligned pointer");
-    const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
-    const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)bias) & 15) == 0);
     hipStream_t s = (hipStream_t)stream;
     const int8_t *xa = (const int8_t *)xq, *wa = (const int8_t *)w;
-    switch (out_dtype) {
-    case ASQ_F32: return launch_fp8_grouped<ASQ_F32>(xa, wa, out, M, N, K, a_scale, w_scale_group, bias, vec_ok, group_offsets, ngroups, s);
-    case ASQ_F16: return launch_fp8_grouped<ASQ_F16>(xa, wa, out, M, N, K, a_scale, w_scale_group, bias, vec_ok, group_offsets, ngroups, s);
-    default: return launch_fp8_grouped<ASQ_BF16>(xa, wa, out, M, N, K, a_scale, w_scale_group, bias, vec_ok, group_offsets, ngroups, s);
-    }
+    return asq_dispatch_dt(out_dtype, [&](auto dt) {
+        return with_fp8_epi<decltype(dt)::value, MmaFp8>(out, N, a_scale, true, 1.0f, 1.0f, w_scale_group, bias, [&](auto epi) {
+            return launch_gemm(xa, wa, M, N, K, epi, s, "asq_linear_fp8_grouped", nullptr, 0, group_offsets, ngroups);
+        });
+    });
 }
 
 extern "C" int asq_quantize_mxfp8(const void *x, int x_dtype, uint8_t *xq, uint8_t *scales, int64_t M, int64_t K, void *stream)
@@ -661,11 +624,7 @@ extern "C" int asq_quantize_mxfp8(const void *x, int x_dtype, uint8_t *xq, uint8
     int64_t blocks = (nb + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipStream_t s = (hipStream_t)stream;
-    switch (x_dtype) {
-    case ASQ_F32: hipLaunchKernelGGL((mx_quant_e4m3<ASQ_F32>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, scales, nb); break;
-    case ASQ_F16: hipLaunchKernelGGL((mx_quant_e4m3<ASQ_F16>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, scales, nb); break;
-    default: hipLaunchKernelGGL((mx_quant_e4m3<ASQ_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, scales, nb); break;
-    }
+    asq_dispatch_dt(x_dtype, [&](auto dt) { hipLaunchKernelGGL((mx_quant_e4m3<decltype(dt)::value>), dim3((unsigned)blocks), dim3(256), 0, s, x, xq, scales, nb); });
     return asq_after_launch(s, "asq_quantize_mxfp8");
 }
 
@@ -685,10 +644,6 @@ extern "C" int asq_linear_mxfp8(const uint8_t *xq, const uint8_t *x_scales, cons
     }
     const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
     ASQ_REQUIRE(grid.y < 65536, ASQ_ERR_DIM, "asq_linear_mxfp8: M too large");
-    switch (out_dtype) {
-    case ASQ_F32: hipLaunchKernelGGL((mx_gemm_e4m3<ASQ_F32>), grid, dim3(256), 0, s, xq, x_scales, wq, w_scales, out, bias, M, N, K); break;
-    case ASQ_F16: hipLaunchKernelGGL((mx_gemm_e4m3<ASQ_F16>), grid, dim3(256), 0, s, xq, x_scales, wq, w_scales, out, bias, M, N, K); break;
-    default: hipLaunchKernelGGL((mx_gemm_e4m3<ASQ_BF16>), grid, dim3(256), 0, s, xq, x_scales, wq, w_scales, out, bias, M, N, K); break;
-    }
+    asq_dispatch_dt(out_dtype, [&](auto dt) { hipLaunchKernelGGL((mx_gemm_e4m3<decltype(dt)::value>), grid, dim3(256), 0, s, xq, x_scales, wq, w_scales, out, bias, M, N, K); });
     return asq_after_launch(s, "asq_linear_mxfp8");
 }

@@ -124,16 +124,11 @@ extern "C" int asq_linear_w8a8(const int8_t *xq, const int8_t *w, void *out, int
     if (rc) return rc;
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(out_dtype)) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8: out misaligned");
     ASQ_REQUIRE((((uintptr_t)s_row | (uintptr_t)s_col | (uintptr_t)bias) & 3) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8: scale/bias misaligned");
-    const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
-    const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)s_col | (uintptr_t)bias) & 15) == 0);
+    const bool vec_ok = epi_vec_ok(out, out_dtype, N, bias, s_col);
     DequantArgs a{xq, w, out, M, N, K, s_scalar, s_row, s_col, bias, order, vec_ok, workspace, workspace_bytes};
     a.out_split = out_split;
     hipStream_t s = (hipStream_t)stream;
-    switch (out_dtype) {
-    case ASQ_F32: return launch_dequant<ASQ_F32>(a, s);
-    case ASQ_F16: return launch_dequant<ASQ_F16>(a, s);
-    default: return launch_dequant<ASQ_BF16>(a, s);
-    }
+    return asq_dispatch_dt(out_dtype, [&](auto dt) { return launch_dequant<decltype(dt)::value>(a, s); });
 }
 
 // ASQ_OFFSETS=0: the module-level paths never use offset operand images (A/B switch; read once)
@@ -175,13 +170,12 @@ extern "C" int asq_linear_w8a8_off(const int8_t *xq_off, const int8_t *w_off, vo
                 "asq_linear_w8a8_off: needs K %% 128 == 0, 128 <= K <= 65536, N %% 4 == 0 and 16-B aligned operands (M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(out_dtype)) == 0 && (((uintptr_t)row_off & 7) == 0) && (((uintptr_t)col_off & 15) == 0), ASQ_ERR_ALIGN, "asq_linear_w8a8_off: out / row_off / col_off misaligned");
     ASQ_REQUIRE((((uintptr_t)s_row | (uintptr_t)s_col | (uintptr_t)bias) & 3) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8_off: scale/bias misaligned");
-    const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
-    const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)s_col | (uintptr_t)bias) & 15) == 0);
+    const bool vec_ok = epi_vec_ok(out, out_dtype, N, bias, s_col);
     DequantArgs a{xq_off, w_off, out, M, N, K, s_scalar, s_row, s_col, bias, order, vec_ok, nullptr, 0};
     a.off = OffsetArgs{row_off, col_off};
     a.out_split = out_split;
     hipStream_t s = (hipStream_t)stream;
-    return out_dtype == ASQ_F16 ? launch_dequant<ASQ_F16>(a, s) : out_dtype == ASQ_BF16 ? launch_dequant<ASQ_BF16>(a, s) : launch_dequant<ASQ_F32>(a, s);
+    return asq_dispatch_dt(out_dtype, [&](auto dt) { return launch_dequant<decltype(dt)::value>(a, s); });
 }
 
 extern "C" int asq_linear_w8a8_q8(const int8_t *xq, const int8_t *w, int8_t *out_q, int mid_dtype, int64_t M, int64_t N, int64_t K, float s_scalar,
@@ -201,11 +195,7 @@ extern "C" int asq_linear_w8a8_q8(const int8_t *xq, const int8_t *w, int8_t *out
     const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out_q & 3) == 0);
     DequantQArgs a{{xq, w, out_q, M, N, K, s_scalar, s_row, s_col, bias, order, vec_ok, workspace, workspace_bytes}, act, qmode, quant_scale};
     hipStream_t s = (hipStream_t)stream;
-    switch (mid_dtype) {
-    case ASQ_F32: return launch_dequant_q<ASQ_F32>(a, s);
-    case ASQ_F16: return launch_dequant_q<ASQ_F16>(a, s);
-    default: return launch_dequant_q<ASQ_BF16>(a, s);
-    }
+    return asq_dispatch_dt(mid_dtype, [&](auto dt) { return launch_dequant_q<decltype(dt)::value>(a, s); });
 }
 
 extern "C" size_t asq_grouped_workspace_bytes(int64_t M, int64_t N, int64_t K, int ngroups)
@@ -255,8 +245,7 @@ static int grouped_impl(const int8_t *xq, const int8_t *w, void *out, int out_dt
     ASQ_REQUIRE(out_dtype == ASQ_F32 || out_dtype == ASQ_F16 || out_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_linear_w8a8_grouped: bad out_dtype %d", out_dtype);
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(out_dtype)) == 0 && ((((uintptr_t)s_row | (uintptr_t)s_group | (uintptr_t)bias | (uintptr_t)group_offsets) & 3) == 0),
                 ASQ_ERR_ALIGN, "asq_linear_w8a8_grouped: misaligned pointer");
-    const size_t vbytes = out_dtype == ASQ_F32 ? 16 : 8;
-    const bool vec_ok = (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)bias) & 15) == 0);
+    const bool vec_ok = epi_vec_ok(out, out_dtype, N, bias);
     ASQ_REQUIRE(workspace == nullptr || (((uintptr_t)workspace) & 255) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8_grouped: workspace must be 256-B aligned");
     DequantArgs a{xq, w, out, M, N, K, 1.0f, s_row, nullptr, bias, ASQ_EPI_SCALE_FIRST, vec_ok, workspace, workspace ? workspace_bytes : 0};
     a.s_group = s_group;
@@ -264,9 +253,5 @@ static int grouped_impl(const int8_t *xq, const int8_t *w, void *out, int out_dt
     a.ngroups = ngroups;
     a.off = OffsetArgs{row_off, col_off};
     hipStream_t s = (hipStream_t)stream;
-    switch (out_dtype) {
-    case ASQ_F32: return launch_dequant<ASQ_F32>(a, s);
-    case ASQ_F16: return launch_dequant<ASQ_F16>(a, s);
-    default: return launch_dequant<ASQ_BF16>(a, s);
-    }
+    return asq_dispatch_dt(out_dtype, [&](auto dt) { return launch_dequant<decltype(dt)::value>(a, s); });
 }

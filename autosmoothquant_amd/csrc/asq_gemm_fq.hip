@@ -66,12 +66,7 @@ static int fused_launch(const void *x, int x_dtype, const int8_t *w, void *out, 
     ASQ_REQUIRE(((uintptr_t)out % asq_dtype_size(x_dtype)) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8_forward: out misaligned");
     ASQ_REQUIRE((((uintptr_t)s_col | (uintptr_t)bias) & 3) == 0, ASQ_ERR_ALIGN, "asq_linear_w8a8_forward: scale/bias misaligned");
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    switch (x_dtype) {
-    case ASQ_F32: rc = launch_skinny_fq<ASQ_F32>(x, w, out, M, N, K, act_mode, quant_scale, s_scalar, s_col, bias, s); break;
-    case ASQ_F16: rc = launch_skinny_fq<ASQ_F16>(x, w, out, M, N, K, act_mode, quant_scale, s_scalar, s_col, bias, s); break;
-    default: rc = launch_skinny_fq<ASQ_BF16>(x, w, out, M, N, K, act_mode, quant_scale, s_scalar, s_col, bias, s); break;
-    }
+    const int rc = asq_dispatch_dt(x_dtype, [&](auto dt) { return launch_skinny_fq<decltype(dt)::value>(x, w, out, M, N, K, act_mode, quant_scale, s_scalar, s_col, bias, s); });
     if (rc) return rc;
     *launched = 1;
     return asq_after_launch(s, "asq_linear_w8a8_forward(fused)");

@@ -159,6 +159,14 @@ template <class T, class F> __device__ __forceinline__ void store4_bounded(T *p,
     if (n + 3 < Ncols) p[3] = value(3);
 }
 
+// Host side, the vec_ok of the functors with a DT output (EpiDequant, EpiFp8): 4 output values go out as one 16-byte (fp32) or 8-byte store and their bias / column
+// scales come in as one 16-byte load, so N % 4 == 0 and every one of these pointers is aligned to its vector (a null bias or s_col counts as aligned).
+static inline bool epi_vec_ok(const void *out, int dt, int64_t N, const float *bias, const float *s_col = nullptr)
+{
+    const size_t vbytes = dt == ASQ_F32 ? 16 : 8;
+    return (N % 4 == 0) && (((uintptr_t)out & (vbytes - 1)) == 0) && ((((uintptr_t)s_col | (uintptr_t)bias) & 15) == 0);
+}
+
 struct EpiI32 {
     using Mma = MmaI8;
     static constexpr bool kHasRow = false, kHasCol = false, kHasBias = false;

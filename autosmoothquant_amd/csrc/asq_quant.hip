@@ -301,16 +301,6 @@ __global__ void __launch_bounds__(256) quant_rows_off(const void *__restrict__ x
 // OFF = false is the plain per-token quantiser (same arithmetic as quant_per_token_cached), OFF = true emits the offset image + row_off.
 // The loads are inline asm and the waits are counted BY HAND (hipcc does not count asm memory operations): with C loads under `if (idx < nvec)` hipcc waited
 // for each load at its branch's join -- ONE load in flight per wave instead of NV (4096 x 4096 fp16 per-token: 13.5 -> 10.7 us, its image 15.4 -> 12.7 us).
-__device__ __forceinline__ void load16_nt_async(v4i &dst, const void *p)
-{
-    asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void pin_vgprs(v4i &x) { asm volatile("" : "+v"(x)); }   // (uses of x stay below this point)
-template <int N> __device__ __forceinline__ void wait_vm()   // at most N vector memory operations still in flight (they retire in issue order)
-{
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // (Tried and dropped: two rows per wave with the second row's loads in flight behind the first row's arithmetic -- 4 .. 10 % SLOWER than one row per wave at
 // every shape, profiles/r4_quantiser_rows.txt: the chip-wide bytes in flight matter more than overlapping a wave's own arithmetic.)
 template <int DT, int NV, class Q, bool PER_TOKEN, bool OFF>
@@ -354,10 +344,7 @@ __global__ void __launch_bounds__(256) quant_rows_wave(const void *__restrict__ 
         };
         if constexpr (PER_TOKEN) {
             static_for<NV>([&](auto ic) { arrive(ic); am.add(v[decltype(ic)::value]); });
-            uint32_t mb = am.f32bits();
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mb = umax32(mb, (uint32_t)__shfl_xor((int)mb, off, 64));
-            const float m = __uint_as_float(mb);
+            const float m = __uint_as_float(wave_umax32(am.f32bits()));
             const float qs = ElemT<DT>::round(m / 127.0f);
             if (lane == 0) s_row[r] = qs;
             const RowDivisor d(qs, m);
@@ -956,11 +943,7 @@ extern "C" int asq_quantize_act(const void *x, int x_dtype, int mode, float quan
     ASQ_REQUIRE(((uintptr_t)x % asq_dtype_size(x_dtype)) == 0, ASQ_ERR_ALIGN, "asq_quantize_act: x misaligned for its dtype");
     ASQ_REQUIRE(mode != ASQ_ACT_PER_TOKEN || ((uintptr_t)s_row % 4) == 0, ASQ_ERR_ALIGN, "asq_quantize_act: s_row misaligned");
     hipStream_t s = (hipStream_t)stream;
-    switch (x_dtype) {
-    case ASQ_F32: return quantize_dt<ASQ_F32>(x, mode, quant_scale, xq, s_row, M, K, s);
-    case ASQ_F16: return quantize_dt<ASQ_F16>(x, mode, quant_scale, xq, s_row, M, K, s);
-    default: return quantize_dt<ASQ_BF16>(x, mode, quant_scale, xq, s_row, M, K, s);
-    }
+    return asq_dispatch_dt(x_dtype, [&](auto dt) { return quantize_dt<decltype(dt)::value>(x, mode, quant_scale, xq, s_row, M, K, s); });
 }
 
 extern "C" int asq_quantize_act_off(const void *x, int x_dtype, int mode, float quant_scale, int8_t *xq, float *s_row, int32_t *row_off,
@@ -979,11 +962,7 @@ extern "C" int asq_quantize_act_off(const void *x, int x_dtype, int mode, float 
                 "asq_quantize_act_off: x must be 16-B aligned, row_off 8-B aligned");
     hipStream_t s = (hipStream_t)stream;
     const int C = offset_cx();
-    switch (x_dtype) {
-    case ASQ_F32: return quantize_off_dt<ASQ_F32>(x, mode, quant_scale, xq, s_row, row_off, M, K, C, s);
-    case ASQ_F16: return quantize_off_dt<ASQ_F16>(x, mode, quant_scale, xq, s_row, row_off, M, K, C, s);
-    default: return quantize_off_dt<ASQ_BF16>(x, mode, quant_scale, xq, s_row, row_off, M, K, C, s);
-    }
+    return asq_dispatch_dt(x_dtype, [&](auto dt) { return quantize_off_dt<decltype(dt)::value>(x, mode, quant_scale, xq, s_row, row_off, M, K, C, s); });
 }
 
 extern "C" int asq_weight_offset_image(const int8_t *w, int64_t N, int64_t K, int8_t *w_off, int32_t *col_off, void *stream)
@@ -1011,17 +990,13 @@ static int norm_quantize_impl(const void *x, int x_dtype, const void *weight, co
                 "asq_norm_quantize: x / weight / bias must be 16-B aligned");
     hipStream_t s = (hipStream_t)stream;
     const int C = offset_cx();
-#define ASQ_NQD(DT_)                                                                                                           \
-    (bias ? (per_token ? launch_norm_quant<DT_, true, true>(x, weight, bias, eps, xq, s_row, M, K, s, nullptr, nullptr, row_off, C)                          \
-                       : launch_norm_quant<DT_, true, false>(x, weight, bias, eps, xq, s_row, M, K, s, nullptr, nullptr, row_off, C))                         \
-          : (per_token ? launch_norm_quant<DT_, false, true>(x, weight, bias, eps, xq, s_row, M, K, s, nullptr, nullptr, row_off, C)                         \
-                       : launch_norm_quant<DT_, false, false>(x, weight, bias, eps, xq, s_row, M, K, s, nullptr, nullptr, row_off, C)))
-    switch (x_dtype) {
-    case ASQ_F32: return ASQ_NQD(ASQ_F32);
-    case ASQ_F16: return ASQ_NQD(ASQ_F16);
-    default: return ASQ_NQD(ASQ_BF16);
-    }
-#undef ASQ_NQD
+    return asq_dispatch_dt(x_dtype, [&](auto dt) {
+        return asq_dispatch_bool(bias != nullptr, [&](auto has_bias) {
+            return asq_dispatch_bool(per_token != 0, [&](auto pt) {
+                return launch_norm_quant<decltype(dt)::value, decltype(has_bias)::value, decltype(pt)::value>(x, weight, bias, eps, xq, s_row, M, K, s, nullptr, nullptr, row_off, C);
+            });
+        });
+    });
 }
 extern "C" int asq_norm_quantize(const void *x, int x_dtype, const void *weight, const void *bias, float eps, int per_token, int8_t *xq,
                                  float *s_row, int64_t M, int64_t K, void *stream)
@@ -1051,17 +1026,13 @@ static int add_norm_quantize_impl(const void *x, const void *residual, void *h_o
                 ASQ_ERR_ALIGN, "asq_add_norm_quantize: x / residual / h_out / weight / bias must be 16-B aligned");
     hipStream_t s = (hipStream_t)stream;
     const int C = offset_cx();
-#define ASQ_ANQ(DT_)                                                                                                                       \
-    (bias ? (per_token ? launch_norm_quant<DT_, true, true, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)               \
-                       : launch_norm_quant<DT_, true, false, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C))             \
-          : (per_token ? launch_norm_quant<DT_, false, true, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)              \
-                       : launch_norm_quant<DT_, false, false, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C)))
-    switch (x_dtype) {
-    case ASQ_F32: return ASQ_ANQ(ASQ_F32);
-    case ASQ_F16: return ASQ_ANQ(ASQ_F16);
-    default: return ASQ_ANQ(ASQ_BF16);
-    }
-#undef ASQ_ANQ
+    return asq_dispatch_dt(x_dtype, [&](auto dt) {
+        return asq_dispatch_bool(bias != nullptr, [&](auto has_bias) {
+            return asq_dispatch_bool(per_token != 0, [&](auto pt) {
+                return launch_norm_quant<decltype(dt)::value, decltype(has_bias)::value, decltype(pt)::value, 1>(x, weight, bias, eps, xq, s_row, M, K, s, residual, h_out, row_off, C);
+            });
+        });
+    });
 }
 extern "C" int asq_add_norm_quantize(const void *x, const void *residual, void *h_out, int x_dtype, const void *weight, const void *bias, float eps,
                                      int per_token, int8_t *xq, float *s_row, int64_t M, int64_t K, void *stream)
@@ -1091,11 +1062,9 @@ extern "C" int asq_dq_add_layernorm_q(const int32_t *x, float x_scale, const voi
     ASQ_REQUIRE(((((uintptr_t)x | (uintptr_t)residual | (uintptr_t)h_out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) && (((uintptr_t)q & (vec - 1)) == 0),
                 ASQ_ERR_ALIGN, "asq_dq_add_layernorm_q: x / residual / h_out / gamma / beta must be 16-B aligned, q %d-B aligned", vec);
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-    case ASQ_F32: return launch_norm_quant<ASQ_F32, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
-    case ASQ_F16: return launch_norm_quant<ASQ_F16, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
-    default: return launch_norm_quant<ASQ_BF16, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
-    }
+    return asq_dispatch_dt(dtype, [&](auto dt) {
+        return launch_norm_quant<decltype(dt)::value, true, false, 2>(x, gamma, beta, eps, q, nullptr, M, K, s, residual, h_out, nullptr, 0, x_scale);
+    });
 }
 
 static int silu_mul_quantize_impl(const void *gate, const void *up, int x_dtype, int per_token, float quant_scale, int8_t *xq, float *s_row, int32_t *row_off,
@@ -1114,17 +1083,13 @@ static int silu_mul_quantize_impl(const void *gate, const void *up, int x_dtype,
     const bool fast = (per_token & ASQ_SILU_FAST) != 0;
     per_token &= 1;
     const int C = offset_cx();
-#define ASQ_SMD(DT_)                                                                                                                              \
-    (fast ? (per_token ? launch_silu_mul_quant<DT_, true, true>(gate, up, quant_scale, xq, s_row, M, K, s, row_off, C)                                        \
-                       : launch_silu_mul_quant<DT_, false, true>(gate, up, quant_scale, xq, s_row, M, K, s, row_off, C))                                     \
-          : (per_token ? launch_silu_mul_quant<DT_, true>(gate, up, quant_scale, xq, s_row, M, K, s, row_off, C)                                              \
-                       : launch_silu_mul_quant<DT_, false>(gate, up, quant_scale, xq, s_row, M, K, s, row_off, C)))
-    switch (x_dtype) {
-    case ASQ_F32: return ASQ_SMD(ASQ_F32);
-    case ASQ_F16: return ASQ_SMD(ASQ_F16);
-    default: return ASQ_SMD(ASQ_BF16);
-    }
-#undef ASQ_SMD
+    return asq_dispatch_dt(x_dtype, [&](auto dt) {
+        return asq_dispatch_bool(per_token != 0, [&](auto pt) {
+            return asq_dispatch_bool(fast, [&](auto fs) {
+                return launch_silu_mul_quant<decltype(dt)::value, decltype(pt)::value, decltype(fs)::value>(gate, up, quant_scale, xq, s_row, M, K, s, row_off, C);
+            });
+        });
+    });
 }
 extern "C" int asq_silu_mul_quantize(const void *gate, const void *up, int x_dtype, int per_token, float quant_scale, int8_t *xq, float *s_row,
                                      int64_t M, int64_t K, void *stream)
@@ -1155,13 +1120,13 @@ extern "C" int asq_rmsnorm(const void *x, int x_dtype, const void *weight, float
     const int64_t nvec = K / vec;
     dim3 grid((unsigned)M), block(256);
 #define ASQ_RN(DT_, NV) hipLaunchKernelGGL((rmsnorm_rows<DT_, NV>), grid, block, 0, s, x, weight, eps, y, (int)K)
-#define ASQ_RN_DT(DT_) do { if (nvec <= 256) ASQ_RN(DT_, 1); else if (nvec <= 512) ASQ_RN(DT_, 2); else if (nvec <= 1024) ASQ_RN(DT_, 4); else ASQ_RN(DT_, 8); } while (0)
-    switch (x_dtype) {
-    case ASQ_F32: ASQ_RN_DT(ASQ_F32); break;
-    case ASQ_F16: ASQ_RN_DT(ASQ_F16); break;
-    default: ASQ_RN_DT(ASQ_BF16); break;
-    }
-#undef ASQ_RN_DT
+    asq_dispatch_dt(x_dtype, [&](auto dt) {
+        constexpr int DT_ = decltype(dt)::value;
+        if (nvec <= 256) ASQ_RN(DT_, 1);
+        else if (nvec <= 512) ASQ_RN(DT_, 2);
+        else if (nvec <= 1024) ASQ_RN(DT_, 4);
+        else ASQ_RN(DT_, 8);
+    });
 #undef ASQ_RN
     return asq_after_launch(s, "asq_rmsnorm");
 }
@@ -1182,13 +1147,10 @@ extern "C" int asq_silu_mul(const void *gate, const void *up, int x_dtype, int f
     int64_t blocks = (nvec + 255) / 256;
     blocks = blocks > 256 * 64 ? 256 * 64 : blocks;
     const bool fast = (flags & ASQ_SILU_FAST) != 0;
-#define ASQ_SM_DT(DT_) do { if (fast) hipLaunchKernelGGL((silu_mul_flat<DT_, true>), dim3((unsigned)blocks), dim3(256), 0, s, gate, up, out, nvec); \
-                            else hipLaunchKernelGGL((silu_mul_flat<DT_, false>), dim3((unsigned)blocks), dim3(256), 0, s, gate, up, out, nvec); } while (0)
-    switch (x_dtype) {
-    case ASQ_F32: ASQ_SM_DT(ASQ_F32); break;
-    case ASQ_F16: ASQ_SM_DT(ASQ_F16); break;
-    default: ASQ_SM_DT(ASQ_BF16); break;
-    }
-#undef ASQ_SM_DT
+    asq_dispatch_dt(x_dtype, [&](auto dt) {
+        asq_dispatch_bool(fast, [&](auto fs) {
+            hipLaunchKernelGGL((silu_mul_flat<decltype(dt)::value, decltype(fs)::value>), dim3((unsigned)blocks), dim3(256), 0, s, gate, up, out, nvec);
+        });
+    });
     return asq_after_launch(s, "asq_silu_mul");
 }

@@ -57,10 +57,8 @@ extern "C" int asq_rope(const void *x, int64_t x_row_pitch, void *out, int x_dty
     const int64_t nwork = B * S * H * (D / 2 / vec);
     int64_t blocks = (nwork + 255) / 256;
     blocks = blocks > 256 * 64 ? 256 * 64 : blocks;   // grid-stride beyond 64 blocks per CU
-    switch (x_dtype) {
-    case ASQ_F32: hipLaunchKernelGGL((rope_kernel<ASQ_F32>), dim3((unsigned)blocks), dim3(256), 0, s, x, out, cos_tab, sin_tab, (int)S, (int)H, (int)D, ld, nwork); break;
-    case ASQ_F16: hipLaunchKernelGGL((rope_kernel<ASQ_F16>), dim3((unsigned)blocks), dim3(256), 0, s, x, out, cos_tab, sin_tab, (int)S, (int)H, (int)D, ld, nwork); break;
-    default: hipLaunchKernelGGL((rope_kernel<ASQ_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, x, out, cos_tab, sin_tab, (int)S, (int)H, (int)D, ld, nwork); break;
-    }
+    asq_dispatch_dt(x_dtype, [&](auto dt) {
+        hipLaunchKernelGGL((rope_kernel<decltype(dt)::value>), dim3((unsigned)blocks), dim3(256), 0, s, x, out, cos_tab, sin_tab, (int)S, (int)H, (int)D, ld, nwork);
+    });
     return asq_after_launch(s, "asq_rope");
 }

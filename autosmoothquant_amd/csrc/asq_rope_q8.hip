@@ -116,10 +116,6 @@ extern "C" int asq_rope_quantize_qkv(const void *q, const void *k, const void *v
     const auto recip = [](float s) { return s > 0x1p-60f && s < 0x1p60f ? 1.0f / s : 0.0f; };   // asq_quantize_act's choice (quantize_dt): QDivFast inside, QDiv outside
     const RopeQ8Args a{(const char *)q, (const char *)k, (const char *)v, (const char *)cos_tab, (const char *)sin_tab, q8, k8, v8, qld, kld, vld, kvb, pos0,
                        heads * (D / 2 / vec), q_scale, recip(q_scale), k_scale, recip(k_scale), v_scale, recip(v_scale), (int)S, (int)Hq, (int)Hkv, (int)D};
-    switch (x_dtype) {
-    case ASQ_F32: launch_rope_q8<ASQ_F32>(a, st); break;
-    case ASQ_F16: launch_rope_q8<ASQ_F16>(a, st); break;
-    default: launch_rope_q8<ASQ_BF16>(a, st); break;
-    }
+    asq_dispatch_dt(x_dtype, [&](auto dt) { launch_rope_q8<decltype(dt)::value>(a, st); });
     return asq_after_launch(st, "asq_rope_quantize_qkv");
 }
