@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from .layers.nn.linear import W8A8BFP32OFP32Linear, W8A8BFP32OFP32LinearWithQuantScale
 from .layers.nn.fused import DeferredResidual
+from .derived import DerivedOperand, scale_vector
 
 
 class RMSNorm(torch.nn.Module):
@@ -142,19 +143,6 @@ def shared_input(x, *mods):
     return mods[0].quantize_input(x, consumers=mods)
 
 
-# ---- independent linears of one input on side streams (measured, OFF by default) ----------------------------------------------------------
-# q/k/v (gate/up) read one activation and write three (two) outputs: nothing orders them but the stream.  On one stream every GEMM ends with a
-# tail (the last tiles draining) and the next one starts with a ramp -- 5-6 us launch to launch at 4096^3 (profiles/r2_clock_power_evidence.md).
-# Forking the 2nd / 3rd module onto side streams and joining afterwards was VERDICT r2's lever 2(c); measured (profiles/r3_gemm_levers.md): the
-# default step goes from 0.2445 to 0.2868 ms (-15 %): three 256-block GEMMs that each want every CU's whole LDS interleave block by block and
-# the fork / join events cost more than the two gaps.  Kept behind ASQ_SIDE_STREAMS=1 for the A/B; results are identical either way.
-import os as _os
-
-SIDE_STREAM_MIN_ROWS = 1024     # below this the GEMMs are short and the fork / join events cost more than the gaps they hide
-side_streams_enabled = _os.environ.get("ASQ_SIDE_STREAMS", "0") == "1"
-_SIDE = {}
-
-
 # ---- same-input linears of equal width as ONE launch with split outputs (ASQ_EPI_OUT_SPLIT) -------------------------------------
 # q/k/v (gate/up) on one stream are three (two) single-round launches of the 256 x 256 kernel, each paying the whole per-launch fixed cost; as one launch over the
 # stacked weights they are a multi-round launch of the persistent kernel, which hides most of it -- and with split outputs every module still gets the dense
@@ -162,7 +150,7 @@ _SIDE = {}
 # ASQ_MERGE_LINEARS=0 keeps the per-module launches (A/B); results are bit-identical either way.
 # Not merged (they run one by one as before): plain-operand runs (ASQ_OFFSETS=0, shapes without images), unequal widths (GQA k / v against q), biased beside
 # bias-free modules, per-token and per-tensor consumers in one run, a single module (o_proj), modules whose own launch already has more than one round of tiles.
-merge_linears_enabled = _os.environ.get("ASQ_MERGE_LINEARS", "1") != "0"
+merge_linears_enabled = os.environ.get("ASQ_MERGE_LINEARS", "1") != "0"
 MERGE_MAX = 4           # ASQ_EPI_OUT_SPLIT(n): n = 2 .. 4
 MERGE_MIN_TILES = 256   # one round of 256 x 256 tiles (one per CU): the merged launch must have more, each module's own launch at most that many
 
@@ -177,10 +165,11 @@ def _merge_key(m):
 
 class _MergedRun:
     """The stacked operand of one run of modules: w [n * N, K] int8 and col [n * N, 2] int32 whose slices ARE the modules' image buffers, and the [n * N] column
-    scales filled from the modules' host scalars (re-keyed on their values, as W8A8BFP32OFP32QKVLinear._scale_vector)."""
+    scales filled from the modules' host scalars (re-keyed on their values: derived.scale_vector)."""
 
     def __init__(self, mods):
         self.mods, self.w, self.col, self.scol, self.bias = tuple(mods), None, None, None, None
+        self.widths = (mods[0].out_features,) * len(mods)
 
     def operands(self, M, dtype, capturing):
         """(w, col) with every module's current image in place, or None (a module without an image; a rebuild needed inside a capture)"""
@@ -220,14 +209,11 @@ class _MergedRun:
         return self.bias
 
     def scales(self, device, capturing):
-        vals = tuple(m._scalar("dequant_scale") for m in self.mods)
-        key = (vals, str(device))
-        if self.scol is None or self.scol[0] != key:
-            if capturing:
-                return None
-            N = self.mods[0].out_features
-            self.scol = (key, torch.cat([torch.full((N,), v, dtype=torch.float32) for v in vals]).to(device))
-        return self.scol[1]
+        hit = scale_vector(self.scol, tuple(m._scalar("dequant_scale") for m in self.mods), self.widths, device, capturing)
+        if hit is None:
+            return None
+        self.scol = hit
+        return hit[1]
 
 
 def _merged_forward(mods, xi):
@@ -274,31 +260,10 @@ def _merged_linears(mods, xi):
 
 
 def concurrent_linears(mods, xi):
-    """[m(xi) for m in mods].  Runs of same-width modules on an offset-image activation go as one split-output launch each (_merged_linears); with
-    ASQ_SIDE_STREAMS=1 modules 2.. run on side streams instead (fork after `xi` is ready on the current stream, join before returning)."""
-    if merge_linears_enabled and not side_streams_enabled and len(mods) >= 2 and getattr(xi, "row_off", None) is not None:
+    """[m(xi) for m in mods].  Runs of same-width modules on an offset-image activation go as one split-output launch each (_merged_linears)."""
+    if merge_linears_enabled and len(mods) >= 2 and getattr(xi, "row_off", None) is not None:
         return _merged_linears(list(mods), xi)
-    t = xi.xq if hasattr(xi, "xq") else xi
-    if (not side_streams_enabled or len(mods) < 2 or not isinstance(t, torch.Tensor) or not t.is_cuda
-            or t.numel() // t.shape[-1] < SIDE_STREAM_MIN_ROWS):
-        return [m(xi) for m in mods]
-    cur = torch.cuda.current_stream(t.device)
-    pool = _SIDE.setdefault((t.device.index, cur.cuda_stream), [])
-    while len(pool) < len(mods) - 1:
-        pool.append(torch.cuda.Stream(device=t.device))
-    fork = torch.cuda.Event()
-    fork.record(cur)
-    outs = [None] * len(mods)
-    for i, m in enumerate(mods[1:], 1):
-        s = pool[i - 1]
-        s.wait_event(fork)
-        with torch.cuda.stream(s):
-            outs[i] = m(xi)
-        outs[i].record_stream(cur)     # allocated on the side stream's pool, consumed (and later freed) on the current stream's timeline
-    outs[0] = mods[0](xi)
-    for s in pool[:len(mods) - 1]:
-        cur.wait_stream(s)
-    return outs
+    return [m(xi) for m in mods]
 
 
 class LlamaLayer(torch.nn.Module):
@@ -419,21 +384,10 @@ def calibrate(layer, h):
 @torch.no_grad()
 def refresh_derived_operands(root):
     """After ANY in-place weight update, before replaying a hipGraph captured on `root` (a layer, a stack of layers, a model): rebuild every operand DERIVED from
-    a weight INTO its existing buffers -- the linears' offset images (_W8A8Base.refresh_offset_image), GateUpSiLU's interleaved gate || up operand and its image
-    (GateUpSiLU.refresh), MixtralLayer's stack images and grouped gate || up operand (MixtralLayer.refresh_offset_images).  A graph bakes those buffers in; an eager
-    forward notices a changed weight by itself (storage + version key), a replay cannot.  Returns the number of operands rebuilt."""
-    from .layers.nn.fused import GateUpSiLU
-    from .layers.nn.linear import _W8A8Base
-    n = 0
-    for m in root.modules():
-        if isinstance(m, _W8A8Base):
-            n += bool(m.refresh_offset_image())
-        elif isinstance(m, GateUpSiLU):
-            n += bool(m.refresh())
-        if isinstance(m, MixtralLayer) and hasattr(m, "_w1_stack"):
-            m.refresh_offset_images()
-            n += 1
-    return n
+    a weight INTO its existing buffers -- whatever each module reports through its `refresh_derived()`: the linears' offset images, GateUpSiLU's interleaved
+    gate || up operand and its image, MixtralLayer's stack images and grouped gate || up operand.  A graph bakes those buffers in; an eager forward notices a changed
+    weight by itself (storage + version key), a replay cannot.  Returns the number of operands rebuilt."""
+    return sum(int(m.refresh_derived()) for m in root.modules() if hasattr(m, "refresh_derived"))
 
 
 @torch.no_grad()
@@ -532,8 +486,7 @@ def per_tensor_twin(mod, input_scale):
     t.dequant_scale = (input_scale * wscale).to(torch.float32)
     t.quant_scale = torch.tensor(input_scale, dtype=torch.float32)
     t._pin_scalars()
-    if "_offset_cache" in mod.__dict__:   # one weight, one image
-        t.__dict__["_offset_cache"] = mod.__dict__["_offset_cache"]
+    t.image = mod.image   # one weight, one image, one rebuild
     return t
 
 
@@ -759,6 +712,14 @@ class ExpertMLP(torch.nn.Module):
         return self.w2(F.silu(self.w1(x)) * self.w3(x))
 
 
+def _stack_offset_image(st, out=None):
+    """ops.weight_offset_image of an [E, N, K] stack: (image int8 [E,N,K], col_off int32 [E,N,2])"""
+    from . import ops
+    E, N, K = st.shape
+    img, col = ops.weight_offset_image(st.view(E * N, K), out=None if out is None else (out[0].view(E * N, K), out[1].view(E * N, 2)))
+    return img.view(E, N, K), col.view(E, N, 2)
+
+
 class MixtralLayer(LlamaLayer):
     def __init__(self, hidden=4096, inter=14336, heads=32, kv_heads=8, experts=8, top_k=2, eps=1e-5, rope_theta=1e6):
         torch.nn.Module.__init__(self)
@@ -796,105 +757,70 @@ class MixtralLayer(LlamaLayer):
             setattr(self, f"_{name}_stack", st)
             setattr(self, f"_{name}_scale", torch.tensor(host, dtype=torch.float32, device=st.device))
             self.__dict__[f"_{name}_scale_host"] = host
+        if "derived" not in self.__dict__:   # (kept across a restack: new stacks of the same shape are imaged into the same buffers)
+            self.derived = {slot: DerivedOperand() for slot in (*self._IMAGE_SLOTS, "w13", "w13_image")}
         return self
+
+    _IMAGE_SLOTS = ("w1", "w3", "w2")   # self.derived[slot]: the image of that expert stack; "w13": the interleaved w1 || w3 operand; "w13_image": its image
+
+    def _derive(self, slot, refresh=False):
+        """self.derived[slot] by the rule of derived.DerivedOperand, its sources, builder and shape stated here once"""
+        from . import ops
+        if slot in self._IMAGE_SLOTS:
+            src = (getattr(self, f"_{slot}_stack"),)
+            rule = (src, _stack_offset_image)
+        else:
+            src = (self._w1_stack, self._w3_stack)
+            E, F_, K = src[0].shape
+            rule = (src, ops.interleave_gate_up_stack, (E, 2 * F_, K)) if slot == "w13" else (src, _stack_offset_image, (E, 2 * F_, K), (self.derived["w13"].buffers,))
+        op = self.derived[slot]
+        got = (op.refresh if refresh else op.get)(*rule)
+        if op.failed and slot != "w13_image":   # (one more int8 copy did not fit: plain operands / the unfused composition from now on)
+            setattr(self, "fuse_gate_up" if slot == "w13" else "offsets", False)
+        return got
 
     def _stack_image(self, name):
         """(image int8 [E,N,K], col_off int32 [E,N,2]) of one expert stack, rebuilt when the stack is (keyed on its storage and version counter)"""
-        from . import ops
-        st = getattr(self, f"_{name}_stack")
-        try:
-            ver = st._version
-        except RuntimeError:
+        img = self._derive(name)
+        if img is None and getattr(self, f"_{name}_stack").is_inference() and not self.derived[name].pinned and not self.__dict__.get("_images_off_logged", False):
             # a stack without a version counter (built under inference_mode): writes into it cannot be seen.  build_offset_images() is the opt-in -- the caller
-            # then owns the refresh (refresh_offset_images), as with _W8A8Base.build_offset_image; otherwise plain operands (logged once)
-            if not self.__dict__.get("_images_pinned", False):
-                if not self.__dict__.get("_images_off_logged", False):
-                    self.__dict__["_images_off_logged"] = True
-                    import logging
-                    logging.getLogger("autosmoothquant_amd").info("MixtralLayer: expert stacks have no version counter (inference tensors): offset images and the grouped "
-                                                                  "gate || up launch are off; call build_offset_images() to opt in (then refresh_offset_images() after weight writes)")
-                return None
-            ver = -1
-        key = (st.data_ptr(), ver, st.device)
-        hit = self.__dict__.get(f"_{name}_image")
-        if hit is None or hit[0] != key:
-            if torch.cuda.is_current_stream_capturing():
-                return None   # (see _W8A8Base.offset_image)
-            E, N, K = st.shape
-            out = None   # rebuild INTO the existing buffers when they still fit: a hipGraph captured on them then replays the new image (ADVICE r4)
-            if hit is not None and hit[1][0].device == st.device and tuple(hit[1][0].shape) == (E, N, K):
-                out = (hit[1][0].view(E * N, K), hit[1][1].view(E * N, 2))
-            try:
-                img, col = ops.weight_offset_image(st.view(E * N, K), out=out)
-            except torch.cuda.OutOfMemoryError:
-                self.offsets = False
-                self.__dict__.pop(f"_{name}_image", None)
-                return None
-            hit = (key, (img.view(E, N, K), col.view(E, N, 2)))
-            self.__dict__[f"_{name}_image"] = hit
-        return hit[1]
+            # then owns the refresh (refresh_offset_images); otherwise plain operands (logged once)
+            self.__dict__["_images_off_logged"] = True
+            import logging
+            logging.getLogger("autosmoothquant_amd").info("MixtralLayer: expert stacks have no version counter (inference tensors): offset images and the grouped "
+                                                          "gate || up launch are off; call build_offset_images() to opt in (then refresh_offset_images() after weight writes)")
+        return img
 
     def _w13_operand(self, want_image):
         """w1 || w3 of every expert interleaved in blocks of 16 channels, [E, 2F, K] (ops.interleave_gate_up_stack), and its offset image when asked for: the operand
         of the grouped gate || up launch (opt-in `fuse_gate_up`: one more int8 copy of the two stacks, plus the image).  Follows the stacks (storage + version)."""
-        from . import ops
-        s1, s3 = self._w1_stack, self._w3_stack
-        try:
-            key = (s1.data_ptr(), s1._version, s3.data_ptr(), s3._version, s1.device)
-        except RuntimeError:
-            if not self.__dict__.get("_images_pinned", False):
-                return None, None
-            key = (s1.data_ptr(), -1, s3.data_ptr(), -1, s1.device)
-        hit = self.__dict__.get("_w13_cache")   # [key, operand, image or None, image is current]
-        if hit is None or hit[0] != key:
-            if torch.cuda.is_current_stream_capturing():
-                return None, None
-            # rebuild INTO the cached buffers when they still fit: a hipGraph captured on them then replays the new weights instead of freed memory (ADVICE r5)
-            E, F_, K = s1.shape
-            fits = hit is not None and hit[1].device == s1.device and tuple(hit[1].shape) == (E, 2 * F_, K)
-            try:
-                w13 = ops.interleave_gate_up_stack(s1, s3, out=hit[1] if fits else None)
-            except torch.cuda.OutOfMemoryError:
-                self.fuse_gate_up = False
-                self.__dict__.pop("_w13_cache", None)
-                return None, None
-            hit = [key, w13, hit[2] if fits else None, False]
-            self.__dict__["_w13_cache"] = hit
-        if want_image and not hit[3]:
-            if torch.cuda.is_current_stream_capturing():
-                return hit[1], None
-            E, N2, K = hit[1].shape
-            out = None if hit[2] is None else (hit[2][0].view(E * N2, K), hit[2][1])
-            try:
-                img, col = ops.weight_offset_image(hit[1].view(E * N2, K), out=out)
-            except torch.cuda.OutOfMemoryError:
-                return hit[1], None
-            hit[2], hit[3] = (img.view(E, N2, K), col), True
-        return hit[1], (hit[2] if (want_image and hit[3]) else None)
+        w13 = self._derive("w13")
+        return w13, (self._derive("w13_image") if want_image and w13 is not None else None)
 
     def build_offset_images(self):
         """Build the three stacks' images (and, with fuse_gate_up, the w1 || w3 operand and its image) now -- load time -- instead of inside the first grouped forward,
         and opt in for stacks without a version counter (a model built under torch.inference_mode()): the caller then calls refresh_offset_images() after writing
-        weights.  Mirrors _W8A8Base.build_offset_image.  Returns True when every image exists."""
-        self.__dict__["_images_pinned"] = True
-        ok = all(self._stack_image(n) is not None for n in ("w1", "w3", "w2"))
+        weights.  Returns True when every image exists."""
+        for op in self.derived.values():
+            op.pin()
+        ok = all(self._stack_image(n) is not None for n in self._IMAGE_SLOTS)
         if getattr(self, "fuse_gate_up", False):
             ok = self._w13_operand(True)[1] is not None and ok
         return ok
 
     def refresh_offset_images(self):
-        """Rebuild the three stacks' images from the current stacks into their existing buffers (after a weight update, before replaying a hipGraph captured
-        on them; see _W8A8Base.refresh_offset_image)."""
-        for name in ("w1", "w3", "w2"):
-            hit = self.__dict__.get(f"_{name}_image")
-            if hit is not None:
-                self.__dict__[f"_{name}_image"] = (None, hit[1])   # (key None never matches: the next _stack_image call rebuilds in place)
-                self._stack_image(name)
-        hit = self.__dict__.get("_w13_cache")   # the grouped gate || up operand and its image follow (same buffers: graphs captured on them stay valid)
-        if hit is not None:
-            had_image = hit[2] is not None
-            hit[0] = None
-            self._w13_operand(had_image)
+        """Rebuild the three stacks' images, the grouped gate || up operand and its image -- those that exist -- from the current stacks into their existing buffers
+        (after a weight update, before replaying a hipGraph captured on them: the buffers stay, so the graph stays valid)."""
+        for slot in (*self._IMAGE_SLOTS, "w13", "w13_image"):
+            if slot != "w13_image" or self.derived["w13"].buffers is not None:
+                self._derive(slot, refresh=True)
+
+    def refresh_derived(self):
+        """(harness.refresh_derived_operands: a layer with expert stacks counts as one)"""
+        if not hasattr(self, "_w1_stack"):
+            return 0
+        self.refresh_offset_images()
+        return 1
 
     def _stacks_current(self):
         """The per-expert modules stay the source of truth (state_dict, load_state_dict, .to(), replica.broadcast_quantized all act on THEIR buffers): the

@@ -9,6 +9,7 @@ share ONE quantised activation and the fp16 norm output never touches HBM."""
 import torch
 
 from ... import ops
+from ...derived import DerivedOperand
 
 
 class QuantizedActivation:
@@ -180,6 +181,7 @@ class GateUpSiLU(torch.nn.Module):
             raise ValueError("GateUpSiLU: gate / up must be bias-free W8A8 linears of one shape and one act_quant")
         self.__dict__["gate"], self.__dict__["up"] = gate, up      # (not registered: this module owns no checkpoint state)
         self.in_features, self.out_features, self.act_quant = gate.in_features, gate.out_features, gate.act_quant
+        self.operand, self.image = DerivedOperand(), DerivedOperand()   # the interleaved gate || up rows, and their offset image
 
     def input_signature(self):
         return self.gate.input_signature()
@@ -189,37 +191,28 @@ class GateUpSiLU(torch.nn.Module):
         return (g._buffers["weight"].is_cuda and g.input_signature() == u.input_signature() and self.out_features % 16 == 0
                 and ops.gate_up_supported(M, self.out_features, self.in_features, dtype))
 
-    def _key(self):
-        return tuple(m._weight_key(m._buffers["weight"]) for m in (self.gate, self.up))
+    def _rule(self, op):
+        """what every call on self.operand / self.image states: the two weights as sources, the builder, the [2F, K] shape (the image reads the operand, not the weights)"""
+        src = (self.gate._buffers["weight"], self.up._buffers["weight"])
+        shape = (2 * self.out_features, self.in_features)
+        if op is self.operand:
+            return src, ops.interleave_gate_up, shape
+        return src, ops.weight_offset_image, shape, (self.operand.buffers,)
 
     def _operand(self):
-        key = self._key()
-        if any(k[1] is None for k in key) and not self.__dict__.get("_pinned", False):
-            return None   # a weight without a version counter: writes into it cannot be seen -> the unfused composition (build() is the opt-in: the caller then owns refresh())
-        if self.__dict__.get("_disabled", False):
-            return None
-        hit = self.__dict__.get("_wgu")
-        if hit is None or hit[0] != key:
-            if torch.cuda.is_current_stream_capturing():
-                return None
-            out = hit[1] if hit is not None and hit[1].device == self.gate.weight.device else None
-            try:
-                hit = (key, ops.interleave_gate_up(self.gate._buffers["weight"], self.up._buffers["weight"], out=out))
-            except torch.cuda.OutOfMemoryError:
-                # one more int8 copy of gate + up did not fit: this module answers None from now on and the caller runs the two linears + silu_mul_q
-                self.__dict__["_disabled"] = True
-                self.__dict__.pop("_wgu", None)
-                self.__dict__.pop("_wgu_image", None)
-                return None
-            self.__dict__["_wgu"] = hit
-            self.__dict__["_wgu_image_key"] = None
-        return hit[1]
+        op = self.operand
+        if op.failed:
+            return None   # one more int8 copy of gate + up did not fit: this module answers None from now on, the caller runs the two linears + silu_mul_q (ADVICE r5)
+        w = op.get(*self._rule(op))
+        if op.failed:
+            self.image = DerivedOperand()
+        return w
 
     def build(self, M=None, dtype=None):
         """Build the interleaved operand now (load time) instead of inside the first forward that can use it, and -- given the (M, dtype) of the forwards to come -- its
         offset image too.  Also the opt-in for weights without a version counter (inference tensors): the caller then calls refresh() after writing them.
         Returns True when the module holds the operand."""
-        self.__dict__["_pinned"] = True
+        self.operand.pin(), self.image.pin()
         ok = self._operand() is not None
         if ok and M is not None and dtype is not None:
             self.offset_image(M, dtype)
@@ -229,40 +222,28 @@ class GateUpSiLU(torch.nn.Module):
         """Rebuild the interleaved operand -- and its offset image, if one exists -- from the CURRENT gate / up weights INTO the existing buffers.  Call after any
         weight update before replaying a hipGraph that was captured on the fused path (the graph bakes these derived buffers in; an eager forward would notice the
         change by itself, a replay cannot), next to gate.refresh_offset_image() / up.refresh_offset_image().  No-op (False) when the
-        module holds no operand."""
-        hit = self.__dict__.get("_wgu")
-        if hit is None or torch.cuda.is_current_stream_capturing():
+        module holds no operand, and inside a capture (both stay marked stale)."""
+        self.image.invalidate()
+        if self.operand.failed or not self.operand.refresh(*self._rule(self.operand)):
             return False
-        self.__dict__["_wgu"] = (None, hit[1])          # (key None never matches: _operand rebuilds into hit[1])
-        had_image = self.__dict__.get("_wgu_image") is not None
-        w = self._operand()
-        if w is None:
-            return False
-        if had_image:
-            old = self.__dict__["_wgu_image"]
-            self.__dict__["_wgu_image"] = ops.weight_offset_image(w, out=old if old[0].device == w.device else None)
-            self.__dict__["_wgu_image_key"] = self._key()
+        self._image(self.image.refresh)
         return True
+
+    refresh_derived = refresh   # (harness.refresh_derived_operands: the operand and its image count as one)
+
+    def _image(self, how):
+        got = how(*self._rule(self.image))
+        if self.image.failed:
+            self.offsets = False   # (a third int8 copy did not fit: the fused GEMM runs on the plain interleaved operand from now on)
+        return got
 
     def offset_image(self, M, dtype):
         """the interleaved operand's offset image when a forward of M rows runs on images, else None (so a fused norm in front emits the activation's image for it)"""
         if not (self.offsets and self.supported(M, dtype) and ops.offsets_supported(int(M), 2 * self.out_features, self.in_features, dtype)):
             return None
-        w = self._operand()
-        if w is None:
+        if self._operand() is None:
             return None
-        if self.__dict__.get("_wgu_image_key") != self._key():
-            if torch.cuda.is_current_stream_capturing():
-                return None
-            old = self.__dict__.get("_wgu_image")
-            try:
-                self.__dict__["_wgu_image"] = ops.weight_offset_image(w, out=old if old is not None and old[0].device == w.device else None)
-            except torch.cuda.OutOfMemoryError:
-                self.offsets = False   # (a third int8 copy did not fit: the fused GEMM runs on the plain interleaved operand from now on)
-                self.__dict__.pop("_wgu_image", None)
-                return None
-            self.__dict__["_wgu_image_key"] = self._key()
-        return self.__dict__["_wgu_image"]
+        return self._image(self.image.get)
 
     @torch.no_grad()
     def forward(self, qa, fast=None, consumer=None):

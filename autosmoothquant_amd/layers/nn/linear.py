@@ -22,6 +22,7 @@ from .. import functional as _F  # noqa: F401  (package marker)
 from ..functional.quantization import quantize_per_tensor_absmax
 from ... import ops
 from ..._CUDA import I8CUGEMM
+from ...derived import DerivedOperand, scale_vector
 from .fused import QuantizedActivation, QuantizedActivationFp8
 
 _ACT_CODE = dict(ops._ACT)   # quantiser mode name -> C-ABI code
@@ -72,6 +73,7 @@ class _W8A8Base(torch.nn.Module):
             self.register_buffer("bias", torch.zeros(out_features, dtype=torch.float32, requires_grad=False))
         for name in self._host_scalars:
             self.register_buffer(name, torch.tensor(1.0, dtype=torch.float32, requires_grad=False))
+        self.image = DerivedOperand()   # the weight's offset image (offset_image below)
 
     # scalar scales stay fp32 on the host; bias stays fp32 (reference :68-81)
     def _pin_scalars(self):
@@ -172,35 +174,21 @@ class _W8A8Base(torch.nn.Module):
     # build_offset_image), kept in ONE pair of buffers for the module's lifetime on a device and rebuilt INTO them when the weight changes
     offsets = True   # class / instance switch (ASQ_OFFSETS=0 in the environment switches the C-ABI side off for the whole process)
 
-    @staticmethod
-    def _weight_key(w):
-        try:
-            ver = w._version
-        except RuntimeError:   # an inference tensor has no version counter: writes into it cannot be seen
-            ver = None
-        return (w.data_ptr(), ver, w.device)
-
-    def _image_buffers(self, w, rebuild_key):
-        """(re)build the image for weight `w`; reuses the module's buffers when they still fit (same shape and device), so a hipGraph captured on them sees the new
-        image at its next replay instead of a freed one.  Allocation failure switches images off for this module: the forward runs on plain operands."""
-        hit = self.__dict__.get("_offset_cache")
-        out = None
-        if hit is not None and hit[1][0].device == w.device and tuple(hit[1][0].shape) == tuple(w.shape):
-            out = hit[1]
-        try:
-            image = ops.weight_offset_image(w, out=out)
-        except torch.cuda.OutOfMemoryError:
-            self.offsets = False   # (a second int8 copy of the weight did not fit: stay on plain operands from now on)
-            self.__dict__.pop("_offset_cache", None)
+    def _image(self, how):
+        """the image through `how` (self.image.get / .refresh / .adopt bound to its leading arguments), or None.  Running out of memory for it switches images off
+        for this module: a second int8 copy of the weight did not fit, the forward stays on plain operands from now on"""
+        w = self._buffers["weight"]
+        if not (self.offsets and w.is_cuda):
             return None
-        self.__dict__["_offset_cache"] = (rebuild_key, image)
-        self.__dict__.pop("_offset_dirty", None)
-        return image
+        got = how((w,), ops.weight_offset_image)
+        if self.image.failed:
+            self.offsets = False
+        return got
 
     def offset_image(self, M, dtype):
         """(w_off int8 [N,K], col_off int32 [N,2]) when a forward of M rows with `dtype` outputs runs on offset operand images, else None.
         The image is a second int8 copy of the weight -- N x K bytes more per module that sees prefill-sized inputs (build_offset_image builds it at load
-        time instead of inside the first such forward).  It is keyed on the weight's storage and version counter: in-place torch operations, .to() and
+        time instead of inside the first such forward).  It follows the weight by the rule of derived.DerivedOperand: in-place torch operations, .to() and
         replica.broadcast_quantized are seen and the image is rebuilt into the same buffers; load_state_dict marks it stale explicitly.
         A weight without a version counter (an inference tensor) gets an image only through build_offset_image(): writes into it are invisible, the caller
         then owns the refresh (refresh_offset_image).
@@ -217,56 +205,41 @@ class _W8A8Base(torch.nn.Module):
             sup = ok[(M, dtype)] = ops.offsets_supported(int(M), self.out_features, self.in_features, dtype)
         if not sup:
             return None
-        key = self._weight_key(w)
-        hit = self.__dict__.get("_offset_cache")
-        if key[1] is None and not self.__dict__.get("_offset_pinned", False):
-            return None   # no version counter and nobody promised to refresh: plain operands
-        if hit is not None and hit[0] == key and not self.__dict__.get("_offset_dirty", False):
-            return hit[1]
-        if torch.cuda.is_current_stream_capturing():
-            return None   # (an image built inside a capture would only exist after the first replay: this capture runs on the plain operands)
-        return self._image_buffers(w, key)
+        image = self.image.get((w,), ops.weight_offset_image)
+        if image is None and self.image.failed:
+            self.offsets = False
+        return image
 
     def build_offset_image(self):
         """Build the image now (load time) instead of lazily inside the first prefill-sized forward: the N x K extra bytes are allocated where an OOM is
         cheap to handle, and a later capture finds the image in place.  Returns True when the module now holds one.  For a weight without a version counter
         (inference tensor) this is also the opt-in: the caller refreshes after writes."""
-        w = self._buffers["weight"]
-        if not (self.offsets and w.is_cuda):
-            return False
-        self.__dict__["_offset_pinned"] = True
-        return self._image_buffers(w, self._weight_key(w)) is not None
+        if self.offsets and self._buffers["weight"].is_cuda:
+            self.image.pin()
+        return self._image(self.image.get) is not None
 
     def refresh_offset_image(self):
         """Rebuild the image from the current weight INTO the existing buffers (one pass over the weight).  Call after a weight update that torch cannot
         see -- a raw pointer write, an external library, copy_ into an inference tensor -- and after ANY weight update before replaying a hipGraph that was
-        captured on the image.  No-op (returns False) when the module holds no image."""
-        w = self._buffers["weight"]
-        if self.__dict__.get("_offset_cache") is None or not (self.offsets and w.is_cuda):
-            return False
-        return self._image_buffers(w, self._weight_key(w)) is not None
+        captured on the image.  No-op (returns False) when the module holds no image, and inside a capture (the image stays marked stale)."""
+        return bool(self._image(self.image.refresh))
 
     def adopt_image_buffers(self, w_off, col_off):
         """Make (w_off int8 [N,K], col_off int32 [N,2]) this module's image buffers and build the image into them now.  For callers that run several modules
         as ONE launch over a stacked operand (harness.concurrent_linears): each module gets its slice of the stack as its buffers, and the module's own key and
         version logic keeps that slice current from then on -- no second copy of the image is kept current.  Buffers the module held before (build_offset_image
-        at load time, an earlier stack) are retired, not freed: graphs captured on them stay valid but see no later weight update.  Returns the image, or None."""
-        w = self._buffers["weight"]
-        if not (self.offsets and w.is_cuda) or w_off.device != w.device or tuple(w_off.shape) != tuple(w.shape):
-            return None
-        hit = self.__dict__.get("_offset_cache")
-        if hit is not None and hit[1][0].data_ptr() != w_off.data_ptr():
-            # the buffers this module held so far stay allocated: a hipGraph captured on them keeps replaying on valid memory (with the image as of now -- they
-            # are no longer refreshed; INTEGRATION.md section 8, "Lifetime of an image")
-            self.__dict__.setdefault("_offset_retired", []).append(hit[1])
-        self.__dict__["_offset_cache"] = (None, (w_off, col_off))   # (no weight has this key: _image_buffers rebuilds, into these buffers)
-        return self._image_buffers(w, self._weight_key(w))
+        at load time, an earlier stack) are retired, not freed: graphs captured on them stay valid but see no later weight update (INTEGRATION.md section 8,
+        "Lifetime of an image").  Returns the image, or None."""
+        return self._image(lambda *rule: self.image.adopt((w_off, col_off), *rule))
 
     def invalidate_offset_image(self):
         """Mark the cached image stale: the next eager forward that wants it rebuilds it into the same buffers.  (In-place torch operations on a weight with a
         version counter, .to() and replica.broadcast_quantized are detected without this; load_state_dict calls it.)"""
-        if self.__dict__.get("_offset_cache") is not None:
-            self.__dict__["_offset_dirty"] = True
+        self.image.invalidate()
+
+    def refresh_derived(self):
+        """what harness.refresh_derived_operands calls on every module that has it: the number of derived operands rebuilt"""
+        return int(self.refresh_offset_image())
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
@@ -405,11 +378,7 @@ class W8A8BFP32OFP32QKVLinear(_W8A8Base):
         self._scol_cache = None
 
     def _scale_vector(self, device):
-        vals = tuple(self._scalar(n) for n in self._host_scalars)
-        key = (vals, tuple(self.qkv_size), str(device))
-        if self._scol_cache is None or self._scol_cache[0] != key:
-            parts = [torch.full((int(n),), v, dtype=torch.float32) for v, n in zip(vals, self.qkv_size)]
-            self._scol_cache = (key, torch.cat(parts).to(device))
+        self._scol_cache = scale_vector(self._scol_cache, tuple(self._scalar(n) for n in self._host_scalars), tuple(self.qkv_size), device)
         return self._scol_cache[1]
 
     def _epilogue_scales(self, device):

@@ -171,7 +171,7 @@ def test_a_graph_captured_before_adoption_keeps_valid_buffers(merged_calls):
     assert equal_lists(harness.concurrent_linears(mods, xi), want) and merged_calls == [3]
     for m, old in zip(mods, own):
         assert m.offset_image(M, torch.float16)[0].data_ptr() != old[0].data_ptr()
-        assert any(r[0] is old[0] and r[1] is old[1] for r in m.__dict__["_offset_retired"])
+        assert any(r[0] is old[0] and r[1] is old[1] for r in m.image.retired)
     del own
     junk = [torch.full((N, K), 77, dtype=torch.int8, device=DEV) for _ in range(6)]      # what freed buffers would be handed out for
     gr.replay()

@@ -307,14 +307,14 @@ def test_no_image_is_built_inside_a_capture():
     for warm in (False, True):
         if warm:
             m(x)
-            assert "_offset_cache" in m.__dict__
+            assert m.image.buffers is not None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         gr = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gr, stream=s):
             got = m(x)
         if not warm:
-            assert m.__dict__.get("_offset_cache") is None
+            assert m.image.buffers is None
         for _ in range(2):
             got.zero_()
             gr.replay()
@@ -368,7 +368,7 @@ def test_fused_llama_layer_with_and_without_images_is_identical():
     q.use_fused = True
     xin = x.half()
     y_img = q(xin)
-    seen = [m for m in q.modules() if isinstance(m, LN._W8A8Base) and m.__dict__.get("_offset_cache") is not None]
+    seen = [m for m in q.modules() if isinstance(m, LN._W8A8Base) and m.image.buffers is not None]
     for m in q.modules():
         if isinstance(m, LN._W8A8Base):
             m.offsets = False

@@ -41,7 +41,7 @@ def _worker(rank, world, port, q):
         m = root["m"]
         x = torch.randint(-3, 4, (2304, 4096), generator=torch.Generator().manual_seed(1)).half().to(dev)
         y_own = m(x)                                   # builds the image of this rank's own weight
-        had_image = m.__dict__.get("_offset_cache") is not None
+        had_image = m.image.buffers is not None
         replica.broadcast_quantized(root, src=0, device=dev)
         y = m(x)                                       # must run on an image of the RECEIVED weight
         img = m.offset_image(2304, torch.float16)

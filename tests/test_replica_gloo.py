@@ -204,9 +204,12 @@ def _worker_mixtral(rank, world, port, q):
         lin.weight = torch.randint(-128, 128, (48, 64), generator=torch.Generator().manual_seed(rank), dtype=torch.int8)
         root = torch.nn.ModuleDict({"layer": layer, "lin": lin})
         assert layer._stacks_current()
-        # a cached offset image on every rank (stand-in tensors: building a real one needs a HIP device; the KEY logic under test is device-agnostic)
-        lin.__dict__["_offset_cache"] = (lin._weight_key(lin.weight), ("image", "col"))
-        key_before = lin.__dict__["_offset_cache"][0]
+        # a cached offset image on every rank (a stand-in builder: a real one needs a HIP device; the KEY logic under test is device-agnostic)
+        torch.cuda.is_current_stream_capturing = lambda: False   # (this worker has no device to ask)
+        builds = []
+        image = lambda w, out=None: builds.append(w.data_ptr()) or (torch.zeros_like(w), torch.zeros(w.shape[0], 2, dtype=torch.int32))
+        assert lin.image.get((lin.weight,), image) is lin.image.get((lin.weight,), image) and len(builds) == 1
+        key_before = lin.image.key
         st_ptr = layer._w1_stack.data_ptr()
         nbytes = replica.broadcast_quantized(root, src=0)
         fp = replica.buffers_fingerprint(root)
@@ -216,7 +219,8 @@ def _worker_mixtral(rank, world, port, q):
         layer.stack_experts()
         restacked = layer._stacks_current() and layer._w1_stack.data_ptr() != st_ptr
         # 2. the module's cached image is keyed on the weight's storage: the arena view is a different storage -> the next offset_image() rebuilds it
-        key_moved = lin._weight_key(lin.weight) != key_before
+        lin.image.get((lin.weight,), image)
+        key_moved = lin.image.key != key_before and len(builds) == 2
         q.put((rank, nbytes, fp, fps, stale, restacked, key_moved, [float(e.w2.dequant_scale) for e in layer.experts], layer._w2_scale.tolist()))
     finally:
         dist.destroy_process_group()
