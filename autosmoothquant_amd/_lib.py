@@ -1,4 +1,4 @@
-"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h and include/asq_hip_attn.h)."""
+"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h and include/asq_hip_decode.h)."""
 import ctypes
 import os
 import threading
@@ -106,6 +106,14 @@ ATTN_SIGNATURES = {
     "asq_rope_quantize_qkv": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _i64, _i64, _i64, _i64, _i64, _vp]),
 }
 
+# include/asq_hip_decode.h: the ragged batched decode step (append at per-sequence device positions, attention over per-sequence lengths), a third table
+# for the same reason: probed by presence, ASQ_VERSION stays
+DECODE_SIGNATURES = {
+    "asq_attn_decode_i8": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
+    "asq_rope_quantize_qkv_at": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _i64, _i64, _i64, _i64, _i64,
+                                        _vp]),
+}
+
 
 def lib():
     """Load libasq_hip.so once.  Fails loudly: there is no fallback implementation."""
@@ -124,7 +132,7 @@ def lib():
                 # imported torch).  The host side above the C-ABI is torch plumbing anyway (ops.py).
                 import torch  # noqa: F401
                 h = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()):
                     fn = getattr(h, name)  # AttributeError if the .so lacks a declared symbol
                     fn.restype, fn.argtypes = res, args
                 if h.asq_version() != ASQ_VERSION:   # a stale build: argument lists and the workspace contract may differ

@@ -1,0 +1,287 @@
+// Decode attention over an int8 KV cache in ONE launch (include/asq_hip_decode.h): one query token per sequence, every sequence with its own number of keys, K and V
+// read where the cache holds them ([B, Smax, Hkv, D] with a batch pitch), grouped-query heads folded.  What a decode step paid before: softmax(Q K^T) as sm128 with
+// M <= 16 rows (a 128-row tile walking its key tiles serially) and P . V as m16kn, two launches with P through memory, on contiguous copies of the cache views.
+//
+// One workgroup per (sequence, KV head); the r = Hq / Hkv query heads of the group are rows 0 .. r - 1 of one 16-row MFMA tile (DESIGN.md 4.9's fold), so K and V are
+// read once per KV head.  All matrix work is v_mfma_i32_16x16x64_i8 (MmaI8x16).  n = the sequence's clamped length, read from the device.
+//   scores  the waves split the 16-key tiles; a wave streams K rows straight into MFMA fragments with 16-B loads (bmm_i8_m16's way: no LDS staging, no barrier inside
+//           the pass), q's fragments stay in registers.  The int32 scores of the r real rows go into an LDS strip [r][chunk] (rows padded by 16 B: a 16-B read of
+//           16 rows at one key offset is conflict-free); each lane keeps its row's integer reference (max of the scores, min for alpha < 0).
+//   sum     the references meet in LDS; l = sum exp2(c * acc + o) over the strip with sm128's formulation (c = alpha * log2 e, o = fl(-float(ref) * c)): every wave
+//           sums its key slices of every row, a fixed butterfly inside the wave, the waves' partials merged in wave order -- deterministic.
+//   P . V   lane (t16, q16) of a wave at K step ks needs P[t16][64 ks + 16 q16 .. + 15] as its A fragment and is the only lane of the workgroup that does: it forms
+//           the 16 bytes from 16 strip entries (one fma(e, 127 / l, 1.5 * 2^23) each, packed as sm128 packs).  P exists neither in memory nor in LDS.  V goes in as
+//           in bmm_i8_m16kn (load4_kn + bmm_transpose4), a wave covering all of D (both 64-byte halves of a 128-byte V row come from one wave); the waves split
+//           the keys and add their int32 partial outputs into an LDS image (integer adds: exact, order-free), then the ASQ_BMM_S8 epilogue and 16-B stores.
+//   long    a sequence that fits one chunk computes its scores once.  A longer one walks its chunks twice: pass 1 with sm128's online reference / rescale rule
+//           (the partial sums are rescaled by exp2(o_new - o_old) when a chunk moves the reference), pass 2 recomputes each chunk's scores and does its P . V.
+// No workgroup waits for another, no workspace, no float atomics.  Rows >= n of the cache are never read (load16_guarded / load4_kn against n).
+#include "asq_bmm_core.h"
+#include "../../include/asq_hip_decode.h"
+
+namespace asq {
+
+// Tuning constants.  The strip budget is the LDS of the scores: 16 rows x 1024 keys, 4 rows x 4096 keys, padded rows included.
+constexpr int DEC_PAD = 4;                                   // ints behind a strip row
+constexpr int DEC_STRIP_BYTES = 16 * (1024 + DEC_PAD) * 4;   // 64.25 KiB
+constexpr int DEC_WAVES = 8;                                 // waves per workgroup of the default launch; ASQ_DECODE_WAVES = 4 / 8 / 16 overrides it (tools/attn_decode_bench.py)
+
+// The LDS of a launch: [strip r x (chunk + DEC_PAD) int32 | output sums r x (64 ND) int32 | wave references NW x 16 | row references 2 x 16 | partial sums 16 x NW]
+__host__ __device__ inline int dec_chunk(int r, int64_t max_len)
+{
+    const int64_t fit = (DEC_STRIP_BYTES / (4 * r) - DEC_PAD) / 64 * 64, need = max_len < 64 ? 64 : (max_len + 63) / 64 * 64;
+    return (int)(need < fit ? need : fit);
+}
+__host__ __device__ inline int dec_lds_bytes(int r, int chunk, int nd, int nw) { return 4 * (r * (chunk + DEC_PAD) + r * 64 * nd + nw * 16 + 32 + 16 * nw); }
+constexpr int DEC_LDS_MAX = DEC_STRIP_BYTES + 4 * (16 * 64 * 4 + 16 * 16 + 32 + 16 * 16);
+
+struct DecArgs {
+    const int8_t *q, *k, *v;
+    const int32_t *kv_len;
+    int8_t *out;
+    int64_t pitch;   // bytes between sequences of k / v
+    int Hq, Hkv, D, r, max_len, chunk;
+    float qk_alpha, pv_alpha;
+};
+
+// ND: 64-byte steps of D (ceil(D / 64)); NW: waves
+template <int ND, int NW> __global__ void __launch_bounds__(64 * NW) attn_decode_i8_kernel(const DecArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) char dec_lds[];
+    constexpr int NT = 64 * NW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, t16 = lane & 15, q16 = lane >> 4;
+    const int r = A.r, D = A.D, C = A.chunk, SP = C + DEC_PAD;
+    int *const strip = (int *)dec_lds, *const osum = strip + r * SP, *const wref = osum + r * 64 * ND, *const rowref = wref + NW * 16;
+    float *const part = (float *)(rowref + 32);
+
+    const int b = blockIdx.x / A.Hkv, g = blockIdx.x - b * A.Hkv;
+    int nb = A.kv_len ? A.kv_len[b] : A.max_len;
+    nb = nb < 0 ? 0 : (nb > A.max_len ? A.max_len : nb);
+    const int64_t ld = (int64_t)A.Hkv * D, qoff = ((int64_t)b * A.Hq + (int64_t)g * r) * D;   // the group's r heads are r * D contiguous bytes of q and out
+    const int8_t *const qb = A.q + qoff, *const kb = A.k + b * A.pitch + (int64_t)g * D, *const vb = A.v + b * A.pitch + (int64_t)g * D;
+    int8_t *const ob = A.out + qoff;
+    if (nb == 0) {   // (the whole workgroup: no barrier has been met)
+        for (int i = tid; i < r * D / 16; i += NT) *(v4i *)(ob + i * 16) = (v4i){0, 0, 0, 0};
+        return;
+    }
+    const bool neg = A.qk_alpha < 0.0f;
+    const float c = A.qk_alpha * SM_LOG2E;
+    const int ref0 = neg ? INT32_MAX : INT32_MIN;
+    auto better = [&](int x, int y) { return neg ? (x < y ? x : y) : (x > y ? x : y); };
+
+    for (int i = tid; i < r * 64 * ND; i += NT) osum[i] = 0;
+    for (int i = tid; i < 16 * NW; i += NT) part[i] = 0.0f;
+    if (tid < 16) rowref[tid] = ref0;
+
+    v4i fq[ND];   // row t16 of the group's q, 16 bytes at 16 q16 of each 64-byte step
+#pragma unroll
+    for (int ds = 0; ds < ND; ++ds) fq[ds] = load16_guarded(qb, D, t16, r, ds * 64 + q16 * 16, D, true);
+
+    // The scores of keys n0 .. n0 + cn - 1 into the strip; returns the lane's reference over its own (row t16, valid keys).  Tile kt of the chunk belongs to wave kt % NW;
+    // a wave has 4 tiles' loads in flight.  A lane's accumulator: row t16, keys 16 kt + 4 q16 .. + 3.
+    auto scores = [&](int n0, int cn) -> int {
+        const int tiles = (cn + 15) >> 4;
+        int tm = ref0;
+        for (int kt0 = wave; kt0 < tiles; kt0 += 4 * NW) {
+            v4i fk[4][ND];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int ds = 0; ds < ND; ++ds) fk[u][ds] = load16_guarded(kb, ld, n0 + (kt0 + u * NW) * 16 + t16, n0 + cn, ds * 64 + q16 * 16, D, true);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int kt = kt0 + u * NW;
+                if (kt < tiles) {
+                    v4i acc = (v4i){0, 0, 0, 0};
+#pragma unroll
+                    for (int ds = 0; ds < ND; ++ds) acc = MmaI8x16::mma(fk[u][ds], fq[ds], acc);
+                    if (t16 < r) {
+                        const int key = kt * 16 + 4 * q16;
+                        *(v4i *)(strip + t16 * SP + key) = acc;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (key + e < cn) tm = better(tm, acc[e]);
+                    }
+                }
+            }
+        }
+        return tm;
+    };
+
+    // ---- pass 1: the row references and sums, chunk by chunk --------------------------------------------------------------------------------------------
+    int par = 0;   // rowref[par * 16 ..]: the references before this chunk, rowref[(par ^ 1) * 16 ..]: with it
+    for (int n0 = 0; n0 < nb; n0 += C) {
+        const int cn = nb - n0 < C ? nb - n0 : C;
+        if (n0 > 0) __syncthreads();   // the previous chunk's sums have read the strip
+        int tm = scores(n0, cn);
+        tm = better(tm, __shfl_xor(tm, 16, 64));
+        tm = better(tm, __shfl_xor(tm, 32, 64));
+        if (q16 == 0) wref[wave * 16 + t16] = tm;
+        __syncthreads();
+        if (tid < 16) {
+            int m = rowref[par * 16 + tid];
+#pragma unroll
+            for (int w = 0; w < NW; ++w) m = better(m, wref[w * 16 + tid]);
+            rowref[(par ^ 1) * 16 + tid] = m;
+        }
+        __syncthreads();
+        for (int row = 0; row < r; ++row) {   // every wave: its key slices of every row
+            const float on = -(float)rowref[(par ^ 1) * 16 + row] * c, oo = -(float)rowref[par * 16 + row] * c;
+            float sum = 0.0f;
+            for (int n = (wave * 64 + lane) * 4; n < cn; n += NT * 4) {
+                const v4i s = *(const v4i *)(strip + row * SP + n);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float ex = __builtin_amdgcn_exp2f(__builtin_fmaf((float)s[e], c, on));
+                    sum += n + e < cn ? ex : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+            if (lane == 0) part[row * NW + wave] = part[row * NW + wave] * __builtin_amdgcn_exp2f(on - oo) + sum;
+        }
+        par ^= 1;
+    }
+    __syncthreads();
+    float o = 0.0f, inv = 0.0f;   // of row t16
+    if (t16 < r) {
+        float l = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) l += part[t16 * NW + w];
+        o = -(float)rowref[par * 16 + t16] * c;
+        inv = l > 0.0f ? 127.0f / l : 0.0f;
+    }
+
+    // ---- pass 2: P . V --------------------------------------------------------------------------------------------------------------------------------------
+    // acc[cb][e][reg] of lane (t16, q16): row t16, column 64 cb + 16 q16 + 4 reg + e (bmm_i8_m16kn's layout per 64-column block)
+    v4i acc[ND][4];
+#pragma unroll
+    for (int cb = 0; cb < ND; ++cb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[cb][e] = (v4i){0, 0, 0, 0};
+    const bool once = nb <= C;   // the strip still holds the only chunk's scores
+    for (int n0 = 0; n0 < nb; n0 += C) {
+        const int cn = nb - n0 < C ? nb - n0 : C;
+        if (!once) {
+            __syncthreads();   // the strip's readers are done
+            scores(n0, cn);
+            __syncthreads();
+        }
+        for (int ks = wave; ks * 64 < cn; ks += NW) {
+            const int key = ks * 64 + q16 * 16;   // the lane's 16 keys, chunk-relative
+            uint32_t rows[ND][16];
+#pragma unroll
+            for (int cb = 0; cb < ND; ++cb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) rows[cb][i] = load4_kn(vb, ld, D, n0 + key + i, n0 + cn, cb * 64 + 4 * t16, true);
+            v4i fp = (v4i){0, 0, 0, 0};
+            if (t16 < r && key < cn) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const v4i s = *(const v4i *)(strip + t16 * SP + key + 4 * w);
+                    uint32_t p[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float ex = __builtin_amdgcn_exp2f(__builtin_fmaf((float)s[e], c, o));
+                        ex = key + 4 * w + e < cn ? ex : 0.0f;
+                        p[e] = __float_as_uint(__builtin_fmaf(ex, inv, SM_MAGIC));   // low byte: rne(127 p), 0 .. 127
+                    }
+                    fp[w] = (int)(__builtin_amdgcn_perm(p[1], p[0], 0x0c0c0400u) | __builtin_amdgcn_perm(p[3], p[2], 0x04000c0cu));
+                }
+            }
+#pragma unroll
+            for (int cb = 0; cb < ND; ++cb) {
+                v4i fw[4];
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    uint32_t d[4];
+                    bmm_transpose4(rows[cb][4 * gq], rows[cb][4 * gq + 1], rows[cb][4 * gq + 2], rows[cb][4 * gq + 3], d);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) fw[e][gq] = (int)d[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[cb][e] = MmaI8x16::mma(fw[e], fp, acc[cb][e]);
+            }
+        }
+    }
+    if (t16 < r) {
+#pragma unroll
+        for (int cb = 0; cb < ND; ++cb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int col = 64 * cb + 16 * q16 + 4 * reg + e;
+                    if (col < D) atomicAdd(osum + t16 * 64 * ND + col, acc[cb][e][reg]);   // LDS integer add: exact, order-free
+                }
+    }
+    __syncthreads();
+    const EpiI8 epi{nullptr, 0, A.pv_alpha, 0.0f, false};   // BmmOut<ASQ_BMM_S8>::one
+    const int chunks = D / 16;
+    for (int i = tid; i < r * chunks; i += NT) {
+        const int row = i / chunks, ch = i - row * chunks;
+        const int *const s = osum + row * 64 * ND + ch * 16;
+        v4i v;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const v4i a = *(const v4i *)(s + 4 * w);
+            v[w] = (int)(((uint32_t)epi.one(a[0], 0) & 0xFF) | (((uint32_t)epi.one(a[1], 0) & 0xFF) << 8) | (((uint32_t)epi.one(a[2], 0) & 0xFF) << 16) |
+                         (((uint32_t)epi.one(a[3], 0) & 0xFF) << 24));
+        }
+        *(v4i *)(ob + row * D + ch * 16) = v;
+    }
+}
+
+static int dec_waves()
+{
+    static const int nw = [] {
+        const char *e = getenv("ASQ_DECODE_WAVES");
+        const int v = e ? atoi(e) : 0;
+        return v == 4 || v == 8 || v == 16 ? v : DEC_WAVES;
+    }();
+    return nw;
+}
+
+template <int ND> static int launch_decode(const DecArgs &a, int64_t grid, hipStream_t s)
+{
+    const int nw = ND > 2 && dec_waves() == 16 ? 8 : dec_waves();   // D > 128 at 16 waves (128 VGPRs) would spill: not instantiated
+    const size_t lds = (size_t)dec_lds_bytes(a.r, a.chunk, ND, nw);
+    const char *const what = "asq_attn_decode_i8";
+    if (nw == 4) return launch_lds(what, attn_decode_i8_kernel<ND, 4>, DEC_LDS_MAX, lds, grid, 256, s, a);
+    if constexpr (ND <= 2)
+        if (nw == 16) return launch_lds(what, attn_decode_i8_kernel<ND, 16>, DEC_LDS_MAX, lds, grid, 1024, s, a);
+    return launch_lds(what, attn_decode_i8_kernel<ND, 8>, DEC_LDS_MAX, lds, grid, 512, s, a);
+}
+
+}  // namespace asq
+using namespace asq;
+
+extern "C" int asq_attn_decode_i8(const int8_t *q, const int8_t *k_cache, const int8_t *v_cache, const int32_t *kv_len, int8_t *out, int64_t B, int64_t Hq, int64_t Hkv,
+                                  int64_t D, int64_t kv_batch_pitch, int64_t max_len, float qk_alpha, float pv_alpha, void *stream)
+{
+    const AsqRange range_("asq_attn_decode_i8");
+    const int64_t lim = 1ll << 31;
+    ASQ_REQUIRE(B >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17), ASQ_ERR_DIM,
+                "asq_attn_decode_i8: bad dims B=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld", (long long)B, (long long)Hq, (long long)Hkv, (long long)D, (long long)max_len);
+    int64_t grid = 0, qn = 0;   // B * Hkv workgroups on a 31-bit grid; B * Hq * D bytes of q and out
+    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &grid) && grid < lim && !__builtin_mul_overflow(B * Hq, D, &qn), ASQ_ERR_DIM, "asq_attn_decode_i8: dims overflow");
+    if (B == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(q && k_cache && v_cache && out, ASQ_ERR_NULL, "asq_attn_decode_i8: NULL pointer");
+    const int64_t cache = max_len * Hkv * D, kvb = kv_batch_pitch == 0 ? cache : kv_batch_pitch;   // (< 2^17 * 2^31 * 2^8)
+    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM, "asq_attn_decode_i8: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)",
+                (long long)Hq, (long long)Hkv, (long long)D);
+    ASQ_REQUIRE(kvb >= cache && kvb % 16 == 0 && kvb <= (1ll << 60) / B, ASQ_ERR_DIM, "asq_attn_decode_i8: kv_batch_pitch must be 0 (dense) or >= max_len * Hkv * D and a multiple of 16");
+    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_cache) | ((uintptr_t)v_cache) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN, "asq_attn_decode_i8: q, the caches and out must be 16-B aligned");
+    ASQ_REQUIRE(((uintptr_t)kv_len & 3) == 0, ASQ_ERR_ALIGN, "asq_attn_decode_i8: kv_len must be 4-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int r = (int)(Hq / Hkv);
+    const DecArgs a{q, k_cache, v_cache, kv_len, out, kvb, (int)Hq, (int)Hkv, (int)D, r, (int)max_len, dec_chunk(r, max_len), qk_alpha, pv_alpha};
+    int rc;
+    switch ((D + 63) / 64) {
+    case 1: rc = launch_decode<1>(a, grid, st); break;
+    case 2: rc = launch_decode<2>(a, grid, st); break;
+    case 3: rc = launch_decode<3>(a, grid, st); break;
+    default: rc = launch_decode<4>(a, grid, st); break;
+    }
+    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_decode_i8");
+}

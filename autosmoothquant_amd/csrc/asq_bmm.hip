@@ -31,7 +31,7 @@
 // step's fragment reads and 16 MFMAs), bmm_stage_off (the output images), bmm_store4 (the finish of m16 / m16kn); on the host bmm_decode (out_kind) and
 // launch_bmm<KIND, KN>, which picks the GROUPED instantiations when the group size is above 1.  The tile puts of t128 and sm128 and the K loops of m16
 // and m16kn stay apart: shared, they would branch on their caller in every line.
-#include "asq_gemm_kernels.h"
+#include "asq_bmm_core.h"
 
 namespace asq {
 
@@ -112,14 +112,7 @@ template <int KIND> __device__ __forceinline__ void bmm_store4(void *out, int64_
     }
 }
 
-// 4 x 4 byte transpose: byte c of r[i] -> byte i of d[c]  (r[i] = 4 consecutive n of k row i  ->  d[c] = 4 consecutive k of column c)
-__device__ __forceinline__ void bmm_transpose4(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t (&d)[4])
-{
-    const uint32_t t0 = __builtin_amdgcn_perm(r1, r0, 0x05010400u), t1 = __builtin_amdgcn_perm(r1, r0, 0x07030602u);   // r0.b0 r1.b0 r0.b1 r1.b1 | .b2 .b3
-    const uint32_t u0 = __builtin_amdgcn_perm(r3, r2, 0x05010400u), u1 = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
-    d[0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u), d[1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
-    d[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u), d[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
-}
+// (bmm_transpose4, the 4 x 4 byte transpose of the KN kinds, and load4_kn: asq_bmm_core.h)
 
 constexpr int BMM_TM = 128, BMM_TN = 128, BMM_TK = 128;
 
@@ -324,17 +317,6 @@ __global__ void __launch_bounds__(256) bmm_i8_m16(const int8_t *__restrict__ a, 
 // lane (t16, q16) is then row t16, column n0 + 4 (4 q16 + reg) + e, so the four MFMAs' registers `reg` are 4 consecutive columns: red[wave][reg][lane].
 constexpr int BMM_KN_TN = 64;
 
-__device__ __forceinline__ uint32_t load4_kn(const int8_t *base, int64_t ld, int64_t N, int64_t k, int64_t K, int64_t n, bool fast)
-{
-    if (k >= K || n >= N) return 0;
-    const int8_t *p = base + k * ld + n;
-    if (fast) return *(const uint32_t *)p;   // N % 16 == 0 (so is the row pitch ld), n % 4 == 0, base 16-B aligned
-    uint32_t w = 0;
-    for (int i = 0; i < 4; ++i)
-        if (n + i < N) w |= (uint32_t)(uint8_t)p[i] << (8 * i);
-    return w;
-}
-
 template <int KIND, bool GROUPED = false, bool TOKEN = false>
 __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a, const int8_t *__restrict__ b, void *__restrict__ out, int64_t M, int64_t N,
                                                     int64_t K, int64_t tiles_n, int64_t total, int64_t group, float alpha, bool fast, bool vec4, BmmTok tok)
@@ -388,8 +370,7 @@ __global__ void __launch_bounds__(256) bmm_i8_m16kn(const int8_t *__restrict__ a
 // Pass 2 recomputes the products and stores rne(exp2(c * acc + o) * (127 / l)) through a [128 rows][128 B] LDS image as whole row segments.
 // An error of o is common to a row's numerators and its sum and cancels.  With K <= 128 the A tile is loaded once and stays in LDS; the first K step of
 // the next tile is in flight during a tile's epilogue.  CAUSAL: tiles no row of the block can see are skipped in both passes (their B rows are never
-// read) and their outputs zero-filled; only tiles cut by the diagonal or by N take the masked epilogue.
-constexpr float SM_LOG2E = 1.44269502162933349609375f, SM_MAGIC = 12582912.0f;   // 1.5 * 2^23: the low mantissa bits of (x + SM_MAGIC) are rne(x)
+// read) and their outputs zero-filled; only tiles cut by the diagonal or by N take the masked epilogue.  (SM_LOG2E, SM_MAGIC: asq_bmm_core.h)
 
 template <bool CAUSAL, bool FAST, bool GROUPED = false, bool TOKEN = false>   // TOKEN: a and b only; the probabilities stay dense for P . V
 __global__ void __launch_bounds__(256, 2) bmm_i8_sm128(const int8_t *__restrict__ a, const int8_t *__restrict__ b, int8_t *__restrict__ out, int64_t M, int64_t N,

@@ -12,7 +12,10 @@ here the first product carries it as its epilogue.  The state dict is the two sc
 following the module dtype, as in layers/nn/bmm.py).
 
 What feeds it for a RoPE model (LLaMA, Mixtral, Baichuan-7B) is RopeQuantQKV: rotary embedding, the per-tensor int8 quantisers of q, k and v and the append to an
-Int8KVCache in one launch (ops.rope_quantize_qkv), straight from the q/k/v projections' [B, S, H, d] outputs into the operands of layout="bshd"."""
+Int8KVCache in one launch (ops.rope_quantize_qkv), straight from the q/k/v projections' [B, S, H, d] outputs into the operands of layout="bshd".
+
+A batch of sequences of different lengths takes a decode step in two launches: RopeQuantQKV with a RaggedInt8KVCache appends one token per sequence at its own
+position (ops.rope_quantize_qkv_at), Int8Attention.decode attends over each sequence's own number of keys on the cache where it lies (ops.attn_decode_i8)."""
 import torch
 
 from ... import ops
@@ -100,6 +103,16 @@ class Int8Attention(torch.nn.Module):
         p = ops.bmm_i8_softmax_q8(q, k, qk_alpha, self.causal, b_group=r)
         return ops.bmm_i8_kn(p, v, torch.int8, pv_alpha, b_group=r, out_token=True, heads=hq)
 
+    def decode(self, q8, k_cache, v_cache, kv_len=None, max_len=None):
+        """One decode step of a ragged batch in ONE launch (ops.attn_decode_i8): q8 int8 [B, 1, Hq, d] -> [B, 1, Hq, d] over k_cache / v_cache [B, Smax, Hkv, d], read
+        where they lie (a RaggedInt8KVCache's k and v, or [:, :n] views), sequence b attending its first kv_len[b] keys (int32 [B] on the device; None: max_len
+        each) with qk_bmm's and pv_bmm's alphas.  A decode step sees every key it is given, so the causal flag does not apply.  max_len: a bound on the lengths
+        (cache.bound()), the caches' rows when absent.  With few sequences x KV heads (a single sequence) the launch leaves most of the chip idle: forward(layout=
+        "bshd") remains the route there."""
+        if not torch.is_tensor(q8) or q8.dim() != 4 or q8.shape[1] != 1:
+            raise ValueError(f"q8 must be [B, 1, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        return ops.attn_decode_i8(q8, k_cache, v_cache, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), max_len=max_len)
+
 
 class Int8KVCache:
     """A preallocated int8 KV cache in the token-major layout: k and v [B, Smax, Hkv, d] and the number of tokens held, `length` (one position for the whole batch).
@@ -132,6 +145,50 @@ class Int8KVCache:
         self.length = 0
 
 
+class RaggedInt8KVCache:
+    """Int8KVCache with a length per sequence: k and v [B, Smax, Hkv, d], `kv_len` int32 [B] on the cache's device -- what the kernels read: the append position of
+    ops.rope_quantize_qkv_at, the number of keys of ops.attn_decode_i8, so a captured step replays as the lengths move -- and its host mirror `lengths`, a list of
+    ints, which serves the bounds checks (ValueError, no device sync).
+    advance(S): S an int (every sequence) or B ints -> lengths += S, one stream-ordered add_ on kv_len.  reset(b=None): every sequence, or sequence b, back to 0
+    (it forgets, it does not clear).  bound() = max(lengths): a tighter max_len for attn_decode_i8 than the capacity."""
+
+    def __init__(self, batch, max_len, kv_heads, head_dim, device=None):
+        self.k = torch.zeros((batch, max_len, kv_heads, head_dim), dtype=torch.int8, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.kv_len = torch.zeros((batch,), dtype=torch.int32, device=device)
+        self.lengths = [0] * batch
+
+    @property
+    def max_len(self):
+        return self.k.shape[1]
+
+    def _steps(self, S):
+        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
+        if len(steps) != len(self.lengths) or any(s < 0 or n + s > self.max_len for s, n in zip(steps, self.lengths)):
+            raise ValueError(f"RaggedInt8KVCache: {steps} more tokens after {self.lengths} do not fit {len(self.lengths)} sequences of max_len {self.max_len}")
+        return steps
+
+    def advance(self, S):
+        steps = self._steps(S)
+        if isinstance(S, int):
+            self.kv_len.add_(S)
+        else:
+            self.kv_len.add_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
+        self.lengths = [n + s for n, s in zip(self.lengths, steps)]
+
+    def reset(self, b=None):
+        if b is None:
+            self.kv_len.zero_()
+            self.lengths = [0] * len(self.lengths)
+        else:
+            b = range(len(self.lengths))[b]   # (IndexError outside, a negative index counts from the end)
+            self.kv_len[b:b + 1].zero_()
+            self.lengths[b] = 0
+
+    def bound(self):
+        return max(self.lengths, default=0)
+
+
 class RopeQuantQKV(torch.nn.Module):
     """Rotary embedding of q and k, the static per-tensor int8 quantisers of q, k and v (x / scale in x's dtype, round, clamp) and the KV-cache append as ONE launch
     (ops.rope_quantize_qkv): every byte is what ops.rope followed by ops.quantize_act(., "per-tensor-div", scale) gives.  The state dict is the three scalar buffers
@@ -142,9 +199,13 @@ class RopeQuantQKV(torch.nn.Module):
     dense tensors.  With an Int8KVCache the position is cache.length (`pos` is not used), k / v are written into cache.slot(S), the cache advances, and k8 / v8 are
     cache.view(): all tokens so far, which Int8Attention(...)(q8, k8, v8, layout="bshd") consumes -- a prefill and every decode step alike.
 
-    Limit: Int8Attention's bshd path needs contiguous K / V, which a cache view is for B == 1 (the single-sequence decode step attention.py documents).  For B > 1 the
-    launch still appends correctly (the cache's batch pitch goes to the kernel), but consuming the view without a copy needs a batch pitch on the token-major b
-    operand of asq_bmm_i8, which it does not have yet: make the views contiguous first."""
+    Int8Attention's bshd path needs contiguous K / V, which a cache view is for B == 1 (the single-sequence decode step attention.py documents); for B > 1 an Int8KVCache
+    still appends correctly (the cache's batch pitch goes to the kernel), but its views are made contiguous before forward(layout="bshd") takes them.
+
+    With a RaggedInt8KVCache (B >= 1 sequences of different lengths) token (b, s) sits at position cache.kv_len[b] + s, read on the device (ops.rope_quantize_qkv_at; `pos`
+    is not used); the cache then advances by `advance` -- S tokens per sequence when absent, an int or B ints otherwise -- and the call returns (q8, cache.k, cache.v),
+    the whole caches, which Int8Attention.decode(q8, cache.k, cache.v, cache.kv_len) reads in place.  A padded prefill is one call on a fresh cache with S = the longest
+    prompt and advance = the true lengths: the next appends overwrite the pad rows, which no decode step reads."""
 
     _SCALES = ("q_scale", "k_scale", "v_scale")
 
@@ -169,11 +230,17 @@ class RopeQuantQKV(torch.nn.Module):
         self._pin()   # a device tensor assigned from outside: one copy, then host reads are free
         return tuple(self._buffers[name].item() for name in self._SCALES)
 
-    def forward(self, q, k, v, cos, sin, pos=0, cache=None):
+    def forward(self, q, k, v, cos, sin, pos=0, cache=None, advance=None):
         qs, ks, vs = self._scales()
         if cache is None:
             return ops.rope_quantize_qkv(q, k, v, cos, sin, qs, ks, vs, pos=pos)
         S = q.shape[1] if torch.is_tensor(q) and q.dim() == 4 else 0
+        if isinstance(cache, RaggedInt8KVCache):
+            cache._steps(S)                                     # the S written rows fit every sequence ...
+            steps = cache._steps(S if advance is None else advance)   # ... and so does what the cache advances by (ValueError before anything is launched)
+            q8, _, _ = ops.rope_quantize_qkv_at(q, k, v, cos, sin, qs, ks, vs, cache.kv_len, cache.k, cache.v)
+            cache.advance(S if advance is None else steps)
+            return q8, cache.k, cache.v
         k_out, v_out = cache.slot(S)
         q8, _, _ = ops.rope_quantize_qkv(q, k, v, cos, sin, qs, ks, vs, pos=cache.length, k_out=k_out, v_out=v_out)
         cache.advance(S)

@@ -772,6 +772,77 @@ def rope_quantize_qkv(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos=0, k_out
     return q8, k8, v8
 
 
+def _kv_cache(t, name, B, Hkv, D):
+    """k_cache / v_cache of the ragged decode ops: an int8 [B, Smax, Hkv, D] tensor with strides (pitch, Hkv * D, D, 1) -- a cache, or a [:, :n] view of one -> (Smax,
+    the batch pitch; 0: one sequence)"""
+    st = t.stride() if isinstance(t, torch.Tensor) and t.dim() == 4 else None
+    if (st is None or t.dtype != torch.int8 or t.shape[0] != B or (Hkv is not None and t.shape[2] != Hkv) or t.shape[3] != D or st[3] != 1 or st[2] != D
+            or (t.shape[1] > 1 and st[1] != t.shape[2] * D) or (B > 1 and (st[0] < t.shape[1] * t.shape[2] * D or st[0] % 16))):
+        raise ValueError(f"{name} must be an int8 [{B}, Smax, {'Hkv' if Hkv is None else Hkv}, {D}] cache (or a [:, :n] view of one) with strides (pitch, Hkv * D, D, 1), pitch >= Smax * Hkv * D "
+                         f"and a multiple of 16, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))} with strides {st}")
+    return t.shape[1], (st[0] if B > 1 else 0)
+
+
+def _kv_caches(k_cache, v_cache, B, Hkv, D):
+    """both caches of one shape and one pitch -> (Smax, Hkv, pitch)"""
+    smax, pitch = _kv_cache(k_cache, "k_cache", B, Hkv, D)
+    if _kv_cache(v_cache, "v_cache", B, k_cache.shape[2], D) != (smax, pitch):
+        raise ValueError(f"k_cache and v_cache must have one shape and one batch pitch, got {list(k_cache.shape)} {k_cache.stride()} and {list(v_cache.shape)} {v_cache.stride()}")
+    return smax, k_cache.shape[2], pitch
+
+
+def rope_quantize_qkv_at(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, k_cache, v_cache):
+    """rope_quantize_qkv with a position per sequence, read on the device (asq_rope_quantize_qkv_at) -> (q8, k_cache, v_cache): token (b, s) is rotated with table row
+    pos[b] + s and its k / v are written to row pos[b] + s of sequence b of the caches.  q, k, v, cos, sin: rope_quantize_qkv's stride rules.  pos: int32 [B] on the
+    device (a captured step replays with moving positions).  k_cache / v_cache: int8 [B, Smax, Hkv, D] with strides (pitch, Hkv * D, D, 1) and one common pitch.
+    A token with pos[b] < 0 or pos[b] + s >= min(T, Smax) writes nothing to the caches and gets a zero q8 row: the device checks, the host never reads pos.
+    Every written byte equals rope_quantize_qkv called per sequence with pos = pos[b]."""
+    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or tuple(k.shape) != (B, S, Hkv, D):
+        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
+    if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or D % 2 or cos.dim() != 2 or sin.shape != cos.shape or cos.shape[1] != D // 2:
+        raise ValueError(f"cos / sin must be [T, {D // 2}] tables, got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
+    T = cos.shape[0]
+    smax, _, kvb = _kv_caches(k_cache, v_cache, B, Hkv, D)
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or tuple(pos.shape) != (B,):
+        raise ValueError(f"pos must be an int32 [{B}] tensor, got {getattr(pos, 'dtype', type(pos))} {list(getattr(pos, 'shape', []))}")
+    _hip(q, "q"), _hip(k, "k"), _hip(v, "v"), _hip(k_cache, "k_cache"), _hip(v_cache, "v_cache")
+    _operand(cos, "cos", q.dtype, T * (D // 2)), _operand(sin, "sin", q.dtype, T * (D // 2)), _operand(pos, "pos", torch.int32, B)
+    _bump_version(k_cache), _bump_version(v_cache)
+    dev = _same_device(q, k, v, cos, sin, pos, k_cache, v_cache)
+    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
+    _launch("asq_rope_quantize_qkv_at", dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[q.dtype], cos.data_ptr(), sin.data_ptr(), T, pos.data_ptr(),
+            q8.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), kvb, smax, float(q_scale), float(k_scale), float(v_scale), B, S, Hq, Hkv, D, _stream(q))
+    return q8, k_cache, v_cache
+
+
+def attn_decode_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, max_len=None):
+    """One decode step of int8 attention for a ragged batch in ONE launch (asq_attn_decode_i8): q int8 [B, Hq, D] or [B, 1, Hq, D], contiguous -> int8 of q's shape.
+    k_cache / v_cache: int8 [B, Smax, Hkv, D] with strides (pitch, Hkv * D, D, 1) -- a cache, or a [:, :n] view of one -- read in place; Hq = r * Hkv, r <= 16, query head
+    h uses KV head h // r.  kv_len: int32 [B] on the device, sequence b attends keys 0 .. clamp(kv_len[b], 0, max_len) - 1 (None: max_len keys each); max_len: a
+    bound on the lengths, Smax when absent.  out = sat_i8(rne(pv_alpha * (P . v))) with P = int8(rne(127 * softmax(qk_alpha * q . k^T))): bmm_i8_softmax_q8 followed by
+    bmm_i8_kn(., torch.int8, pv_alpha), P never leaving the chip.  Shapes and strides are checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or q.dim() not in (3, 4) or (q.dim() == 4 and q.shape[1] != 1) or not q.is_contiguous():
+        raise ValueError(f"q must be a contiguous int8 [B, Hq, D] or [B, 1, Hq, D] tensor, got {getattr(q, 'dtype', type(q))} {list(getattr(q, 'shape', []))}")
+    B, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
+    smax, Hkv, kvb = _kv_caches(k_cache, v_cache, B, None, D)
+    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
+        raise ValueError(f"q has {Hq} heads of {D}, the caches {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
+    max_len = smax if max_len is None else int(max_len)
+    if not 0 <= max_len <= smax or max_len >= 1 << 17:
+        raise ValueError(f"max_len {max_len} must be within the caches' {smax} rows and below 2^17")
+    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
+        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
+    _dev(q, "q"), _hip(k_cache, "k_cache"), _hip(v_cache, "v_cache"), _operand(kv_len, "kv_len", torch.int32, B, optional=True)
+    dev = _same_device(q, k_cache, v_cache, kv_len)
+    out = torch.empty_like(q)
+    _launch("asq_attn_decode_i8", dev, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(kv_len), out.data_ptr(), B, Hq, Hkv, D, kvb, max_len,
+            float(qk_alpha), float(pv_alpha), _stream(q))
+    return out
+
+
 def silu_mul_quantize_fp8(gate, up, fast=None):
     """e4m3(per-token quantise(silu(gate) * up)) in ONE pass (asq_silu_mul_quantize_fp8): (xq float8_e4m3fn [M,K], scale f32 [M,1]) -- what
     quantize_act_fp8(F.silu(gate) * up, "per-token") returns from three.  fast as in silu_mul_quantize (default: the hardware-transcendental SiLU; False: the
