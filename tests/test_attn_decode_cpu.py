@@ -1,7 +1,9 @@
 """CPU: the third C-ABI header (include/asq_hip_decode.h) and its loader table with the discipline tests/test_rope_q8_cpu.py keeps over the second, the argument
 rules of asq_attn_decode_i8 and asq_rope_quantize_qkv_at in their stated order (NULL and made-up pointers: nothing is launched), the refusals of the ops and the
-modules, RaggedInt8KVCache's bookkeeping, and the yardstick of the GPU test: tests/attn_decode_ref.py's caps for every case, and its intervals collapsing to exact
-values on the constructed cases."""
+modules, RaggedInt8KVCache's bookkeeping, and the yardstick of the GPU test: tests/attn_decode_ref.py's chunk() pinned to the constants of csrc/asq_attn_decode.hip
+and to DESIGN.md 4.12's figures, its caps for every case and sign, its intervals collapsing to exact values on the constructed cases (uniform, one-hot per r and per D,
+the key-position walk for 4 / 8 / 16 waves, the two weights under both signs), and the teeth of those cases: the float32 model chunked_probs() passes every
+constructed and chunked case as it is and is rejected on a named case with each of its five defects."""
 import os
 import re
 
@@ -202,16 +204,51 @@ def test_ragged_cache_bookkeeping():
     assert c.kv_len.data_ptr() == ptr                           # the device tensor a captured step reads stays where it is
 
 
-@pytest.mark.parametrize("p", R.PARAMS, ids=[R.param_id(p) for p in R.PARAMS])
-def test_the_yardstick_keeps_its_caps_on_every_gpu_case(p):
+def _constant(src, name):
+    expr = re.search(rf"constexpr int {name} = ([^;]+);", src).group(1)
+    assert re.fullmatch(r"[0-9A-Z_ ()+*]+", expr), expr
+    return expr
+
+
+def test_chunk_restates_dec_chunk_and_the_documented_figures():
+    src = open(os.path.join(ROOT, "autosmoothquant_amd", "csrc", "asq_attn_decode.hip")).read()
+    pad = int(_constant(src, "DEC_PAD"))
+    strip = eval(_constant(src, "DEC_STRIP_BYTES"), {"DEC_PAD": pad})
+    assert (pad, strip) == (R.DEC_PAD, R.DEC_STRIP_BYTES), "the strip budget of asq_attn_decode.hip moved: tests/attn_decode_ref.py restates it, and every edge case is derived from it"
+    body = src[src.index("inline int dec_chunk(int r, int64_t max_len)"):]
+    body = body[:body.index("}")]
+    assert "fit = (DEC_STRIP_BYTES / (4 * r) - DEC_PAD) / 64 * 64" in body and "need = max_len < 64 ? 64 : (max_len + 63) / 64 * 64" in body and "need < fit ? need : fit" in body
+    top = R.MAX_LEN_LIMIT
+    assert "max_len < (1ll << 17)" in src and top == (1 << 17) - 1
+    assert [R.chunk(r, top) for r in (16, 12, 8, 7, 4, 3, 1)] == [1024, 1344, 2048, 2304, 4096, 5440, 16384]       # 1024 at r = 16, 4096 at r = 4
+    assert "(1024 keys at r = 16, 4096 at r = 4, never" in open(os.path.join(ROOT, "DESIGN.md")).read()
+    for r in range(1, 17):
+        fit = R.chunk(r, top)
+        assert fit % 64 == 0 and 4 * r * (fit + pad) <= strip < 4 * r * (fit + 64 + pad)
+        assert [R.chunk(r, n) for n in (0, 1, 64, 65, fit - 1, fit, fit + 1)] == [64, 64, 64, 128, fit, fit, fit]
+    # what the case tables promise about themselves
+    forms = {((R.CASES[ci][2] + 63) // 64, R.chunked(ci)) for ci in range(len(R.CASES))}
+    assert forms == {(nd, ch) for nd in (1, 2, 3, 4) for ch in (False, True)}
+    assert {R.CASES[ci][1] for ci in range(len(R.CASES))} >= {1, 2, 3, 4, 5, 6, 7, 8, 12, 16}
+    assert sorted({ci for ci, _ in R.NEG_PARAMS}) == [ci for ci in range(R.NEW_CASES, len(R.CASES)) if max(R.CASES[ci][3]) > R.chunk(R.CASES[ci][1], max(R.CASES[ci][3]) + 3)]
+    assert len({ci for ci, _ in R.NEG_PARAMS}) == 6
+    for ci in R.POISONED[2:]:
+        assert R.chunked(ci)
+
+
+SIGNED = [(p, 1) for p in R.PARAMS] + [(p, -1) for p in R.NEG_PARAMS]
+
+
+@pytest.mark.parametrize("p,sign", SIGNED, ids=[R.param_id(p) + ("-neg" if sign < 0 else "") for p, sign in SIGNED])
+def test_the_yardstick_keeps_its_caps_on_every_gpu_case(p, sign):
     case, si = p
-    s_lo, s_hi, nband, total = R.case_sums(case, si)
+    s_lo, s_hi, nband, total = R.case_sums(case, si, sign)
     assert total == sum(R.CASES[case][0] * R.CASES[case][1] * n for n in R.CASES[case][3])
     for pv in R.PV_ALPHAS:
         lo, hi = R.interval(s_lo, s_hi, pv)
-        amb = R.caps(lo, hi, nband, total, f"{R.param_id(p)} pv_alpha {pv:.5f}")
+        amb = R.caps(lo, hi, nband, total, f"{R.param_id(p)} sign {sign:+d} pv_alpha {pv:.5f}")
         assert (lo <= hi).all()
-        print(f"{R.param_id(p)} pv_alpha {pv:.5f}: band {nband} / {total}, ambiguous outputs {amb} / {lo.size}")
+        print(f"{R.param_id(p)} sign {sign:+d} pv_alpha {pv:.5f}: band {nband} / {total}, ambiguous outputs {amb} / {lo.size}")
 
 
 def test_the_reference_is_exact_on_the_constructed_cases():
@@ -234,3 +271,144 @@ def test_the_reference_is_exact_on_the_constructed_cases():
                 s = k[b, :n, h // r].astype(np.int64) @ q[b, h].astype(np.int64)
                 rest = np.delete(s, hot[b, h])
                 assert rest.size == 0 or (s[hot[b, h]] - rest.max()) * alpha > 20
+
+
+def _exact(q, k, v, lengths, alpha, want, what, pvs=(1.0 / 127, 0.003)):
+    """the yardstick leaves no room on a constructed case: no P element in the band, s_lo == s_hi, the interval is the one promised value"""
+    s_lo, s_hi, nband, total = R.sums(q, k, v, lengths, alpha)
+    assert nband == 0 and total > 0 and np.array_equal(s_lo, s_hi), what
+    for pv in pvs:
+        lo, hi = R.interval(s_lo, s_hi, pv)
+        assert np.array_equal(lo, hi) and np.array_equal(lo, want(pv)), what
+
+
+def _margin(q, k, lengths, alpha, keys, what, least=20):
+    """the keys named per (sequence, head) lead every other key of their row by more than `least` / |qk_alpha| (towards the minimum for a negative alpha)"""
+    r = q.shape[1] // k.shape[2]
+    sign = 1 if alpha > 0 else -1
+    for b, n in enumerate(lengths):
+        for h in range(q.shape[1]):
+            s = sign * (k[b, :n, h // r].astype(np.int64) @ q[b, h].astype(np.int64))
+            named = sorted(set(keys(b, h)))
+            rest = np.delete(s, named)
+            assert rest.size == 0 or (s[named].min() - rest.max()) * abs(alpha) > least, what
+
+
+def test_one_hot_per_r_and_per_d_is_exact():
+    assert [s[1] for s in R.ONE_HOT_R] == list(range(1, 17)) and [s[2] for s in R.ONE_HOT_D] == list(range(16, 257, 16))
+    for shapes, make in ((R.ONE_HOT_R, R.one_hot_r_case), (R.ONE_HOT_D, R.one_hot_d_case)):
+        for i, shape in enumerate(shapes):
+            q, k, v, lengths, alpha, ml, hot = make(i)
+            assert list(lengths) == [5, 300] and q.shape[1:] == (shape[0] * shape[1], shape[2])
+            _exact(q, k, v, lengths, alpha, lambda pv: R.one_hot_expected(v, hot, pv), shape)
+            _margin(q, k, lengths, alpha, lambda b, h: [hot[b, h]], shape)
+
+
+@pytest.mark.parametrize("nw", [4, 8, 16])
+@pytest.mark.parametrize("i", range(len(R.WALK)))
+def test_the_key_position_walk_is_exact(i, nw):
+    hkv, r, d, tail = R.WALK[i]
+    n, C, pos = R.walk_positions(r, nw, tail)
+    assert C == R.chunk(r, n + 3) and n == 2 * C + 37 and n % 16 != 0
+    want = {C - 65, C - 64, C - 17, C - 16, C - 1, C, C + 1, C + 15, C + 16, C + 63, C + 64, 2 * C - 1, 2 * C, n - 17, n - 16, n - 1}
+    if not tail:
+        want |= {0, 1, 15, 16, 17, 63, 64, 65, 16 * nw - 1, 16 * nw, 64 * nw - 1, 64 * nw}
+    assert set(pos) == want and len(pos) == len(set(pos))
+    if nw != 8 and tail:
+        return                                                  # the r = 1 positions do not depend on the waves: the same case as at 8
+    q, k, v, lengths, alpha, ml, hot = R.walk_case(i, nw)
+    assert lengths == (n,) * len(pos) and ml == n + 3 and (hot == np.array(pos)[:, None]).all() and k.shape[1] == ml + 2
+    if tail:
+        assert (C, n) == (16384, 32805) and k.nbytes < 36 << 20
+    _exact(q, k, v, lengths, alpha, lambda pv: R.one_hot_expected(v, hot, pv), R.WALK[i])
+    assert np.array_equal(R.one_hot_expected(v, hot, 1.0 / 127), np.stack([v[b, p].repeat(r, axis=0) for b, p in enumerate(pos)]))       # 127 v / 127: v itself
+    _margin(q, k, lengths, alpha, lambda b, h: [hot[b, h]], R.WALK[i])
+
+
+@pytest.mark.parametrize("neg", [False, True], ids=["pos", "neg"])
+@pytest.mark.parametrize("i", range(len(R.WALK)))
+def test_the_two_weights_are_exact(i, neg):
+    hkv, r, d, tail = R.WALK[i]
+    q, k, v, lengths, alpha, ml, places = R.two_weight_case(i, neg)
+    n = lengths[0]
+    C = R.chunk(r, ml)
+    assert (alpha < 0) == neg and n > C and (n == 20000) == tail
+    assert [(pa // C, pb // C) for pa, pb in places] == [(0, (n - 1) // C), ((n - 1) // C, 0), (0, 1), (1, 0), (1, 1)]
+    assert places[2] == (C - 1, C) and places[3] == (C, C - 1)
+    _exact(q, k, v, lengths, alpha, lambda pv: R.two_weight_expected(v, places, r, pv), (R.WALK[i], neg))
+    _margin(q, k, lengths, alpha, lambda b, h: places[b], (R.WALK[i], neg), least=40)
+    for b, (pa, pb) in enumerate(places):                       # A trails B by exactly 400 on every row: one natural unit at qk_alpha = 1 / 400
+        sa, sb = (k[b, p, 0].astype(np.int64) @ q[b].astype(np.int64).T for p in (pa, pb))
+        assert ((sb - sa) * (-1 if neg else 1) == 400).all() and abs(alpha) == 1.0 / 400
+    t = 127 * np.exp([-1.0, 0.0]) / (1 + np.exp(-1.0))
+    assert tuple(np.rint(t).astype(int)) == R.TWO_WEIGHTS and (np.abs(t - np.floor(t) - 0.5) > 0.34).all() and R.SR.band_width(20000) * 93 < 0.23
+
+
+def test_the_poisoned_tail_wins_its_row_outright():
+    for case in R.POISONED:
+        hkv, r, d, lengths = R.CASES[case]
+        q, _, _, _ = R.operands(case)
+        k2, v2, k0, v0, kv_len, n_b = R.poisoned(case)
+        ml = R.max_len(lengths)
+        assert kv_len[0] > ml and n_b[0] == ml and list(n_b[1:]) == list(kv_len[1:]) == list(lengths[1:]) and k2.shape[1] == ml + 2
+        for b, n in enumerate(n_b):
+            assert np.array_equal(k2[b, :n], k0[b, :n]) and np.array_equal(v2[b, :n], v0[b, :n]) and not k0[b, n:].any() and not v0[b, n:].any()
+            assert (np.abs(v2[b, n:]) == 127).all() and n < k2.shape[1]
+            for g in range(hkv):
+                row = g * r + n % r
+                assert k2[b, n, g].astype(np.int64) @ q[b, row].astype(np.int64) == 127 * np.abs(q[b, row].astype(np.int64)).sum()       # the most any key can score
+        s_lo, s_hi, nband, total = R.poisoned_sums(case)        # the yardstick's caps at the clamped lengths the GPU test judges by
+        amb = R.caps(*R.interval(s_lo, s_hi, R.PV_ALPHAS[0]), nband, total, f"poisoned case {case}")
+        print(f"poisoned case {case}: band {nband} / {total}, ambiguous outputs {amb} / {s_lo.size}")
+
+
+def _model_cases():
+    """(name, q, k, v, lengths, qk_alpha, max_len, (s_lo, s_hi), with defects): the constructed chunked cases, and the chunked interval cases (the defects at the middle
+    score deviation only: the faithful model is what has to pass everywhere)"""
+    for i in range(len(R.WALK) - 1):                            # (the r = 1 shapes run on the device; their rows are no different to the model)
+        q, k, v, lengths, alpha, ml, _ = R.walk_case(i)
+        yield f"walk {R.WALK[i][:3]}", q, k, v, lengths, alpha, ml, R.sums(q, k, v, lengths, alpha)[:2], True
+        for neg in (False, True):
+            q, k, v, lengths, alpha, ml, _ = R.two_weight_case(i, neg)
+            yield f"two weights {R.WALK[i][:3]} {'-' if neg else '+'}", q, k, v, lengths, alpha, ml, R.sums(q, k, v, lengths, alpha)[:2], True
+    for ci in range(len(R.CASES)):
+        if R.chunked(ci):
+            q, k, v, lengths = R.operands(ci)
+            for si in range(len(R.SDS)):
+                for sign in (1, -1) if ci >= R.NEW_CASES else (1,):
+                    yield f"{R.CASES[ci][:3]} sd {R.SDS[si]:g} {'-' if sign < 0 else '+'}", q, k, v, lengths, sign * R.qk_alpha(ci, si), R.max_len(lengths), R.case_sums(ci, si, sign)[:2], si == 1
+
+
+def _outside(out, lo, hi):
+    out = out.astype(np.int64)
+    return int(((out < lo) | (out > hi)).sum())
+
+
+def test_the_model_passes_and_each_defect_is_caught():
+    pv = R.PV_ALPHAS[0]
+    caught = {d: [] for d in R.DEFECTS}
+    for name, q, k, v, lengths, alpha, ml, s, with_defects in _model_cases():
+        lo, hi = R.interval(*s, pv)
+        R.check(R.model_out(q, k, v, lengths, alpha, pv, ml), lo, hi, f"the faithful model on {name}")
+        for d in R.DEFECTS[:4] if with_defects else ():
+            if _outside(R.model_out(q, k, v, lengths, alpha, pv, ml, d), lo, hi):
+                caught[d].append(name)
+    for case in R.POISONED:
+        q = R.operands(case)[0]
+        k2, v2, _, _, _, n_b = R.poisoned(case)
+        ml, alpha = R.max_len(R.CASES[case][3]), R.qk_alpha(case, 1)
+        lo, hi = R.interval(*R.poisoned_sums(case)[:2], pv)
+        R.check(R.model_out(q, k2, v2, n_b, alpha, pv, ml), lo, hi, f"the faithful model on the poisoned case {case}")
+        if _outside(R.model_out(q, k2, v2, n_b, alpha, pv, ml, "tail_plus_one"), lo, hi):
+            caught["tail_plus_one"].append(f"poisoned {case}")
+    for d, names in caught.items():
+        print(f"{d}: caught on {len(names)} cases: {names}")
+    two = [f"two weights {w[:3]} {s}" for w in R.WALK[:-1] for s in "+-"]
+    walks = [f"walk {w[:3]}" for w in R.WALK[:-1]]
+    # random data shows a missing or stale rescale where a later chunk is long enough to move a row's reference: the cases with a sequence of two full chunks or more
+    moving = [f"{shape} sd 4 {s}" for shape in ((1, 16, 256), (1, 8, 128), (2, 4, 128), (1, 12, 64)) for s in "+-"]
+    for d, must in (("no_rescale", two + moving), ("stale_reference", two + moving), ("edge_twice", two), ("drop_last_tile", walks),
+                    ("tail_plus_one", [f"poisoned {c}" for c in R.POISONED])):
+        missed = [n for n in must if n not in caught[d]]
+        assert not missed, f"the defect {d} passes on {missed}"
+

@@ -1,52 +1,43 @@
 """GPU: asq_attn_decode_i8 through ops.attn_decode_i8 / Int8Attention.decode (include/asq_hip_decode.h).
 
-  * every case of tests/attn_decode_ref.py by its interval rule, within its caps;
-  * two constructed families that are exact by design (uniform softmax, one-hot), bit for bit: head mapping, lengths, addressing, epilogue;
-  * the rows behind a sequence's length and the pitch gap under two random fills: the outputs must not move;
+  * every case of tests/attn_decode_ref.py by its interval rule, within its caps: ceil(D / 64) of 1 to 4, each on the one-pass and on the chunked path, r that are no
+    powers of two; the second group's chunked cases under -qk_alpha as well (the min reference moving between chunks);
+  * constructed families that are exact by design, bit for bit: uniform softmax; one-hot, also once per r = 1 .. 16 and once per D = 16 .. 256 (head mapping,
+    lengths, addressing, epilogue); the key-position walk (one weight per sequence on every seam of the loops: tile, K step, wave strides, chunk edges, last partial
+    tile); two weights in different chunks under both signs (the rescale, exactly: 34 v[A] + 93 v[B]);
+  * the rows behind a sequence's length and the pitch gap under two random fills, and poisoned with the key that would win a row: the outputs must not move;
+  * the 4-wave and 16-wave kernels (ASQ_DECODE_WAVES is read once per process) in a child process each: tests/attn_decode_child.py;
   * kv_len None / above max_len / negative, a negative qk_alpha;
   * against Int8Attention.forward(layout="bshd") on contiguous copies; a ragged prefill + three decode steps end to end against single-sequence runs;
   * the gate: at the bench shape the launch on the cache in place beats what a B > 1 caller paid before (two copies + the two-launch forward)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
+import attn_decode_child as CH
 import attn_decode_ref as R
 from autosmoothquant_amd import ops
 from bmm_ref import assert_bits_equal, medians_us, ref_out
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _dev(*arrays):
-    return [torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays]
-
-
-def _run(q, k, v, lengths, qk_alpha, pv_alpha, max_len, kv_len="lengths"):
-    """k, v: [B, rows, Hkv, D] device buffers, passed as their [:, :max_len] views (the pitch is rows >= max_len rows)"""
-    if isinstance(kv_len, str):
-        kv_len = torch.tensor(lengths, dtype=torch.int32, device=DEV)
-    out = ops.attn_decode_i8(q, k[:, :max_len], v[:, :max_len], kv_len, qk_alpha, pv_alpha)
-    assert out.dtype == torch.int8 and out.shape == q.shape and out.is_contiguous()
-    return out.cpu().numpy()
+DEV = CH.DEV
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_dev, _run = CH.dev, CH.run       # (the device runs that the wave children repeat live in tests/attn_decode_child.py)
 
 
 @pytest.mark.parametrize("p", R.PARAMS, ids=[R.param_id(p) for p in R.PARAMS])
 def test_cases_by_the_interval_rule(p):
-    case, si = p
-    qn, kn, vn, lengths = R.operands(case)
-    q, k, v = _dev(qn, kn, vn)
-    s_lo, s_hi, nband, total = R.case_sums(case, si)
-    for pv in R.PV_ALPHAS:
-        what = f"{R.param_id(p)} pv_alpha {pv:.5f}"
-        lo, hi = R.interval(s_lo, s_hi, pv)
-        amb = R.caps(lo, hi, nband, total, what)
-        out = _run(q, k, v, lengths, R.qk_alpha(case, si), pv, R.max_len(lengths))
-        print(f"{what}: {nband} of {total} P elements in the band, {amb} of {lo.size} outputs with lo != hi, {int((out != lo).sum())} outputs != lo")
-        R.check(out, lo, hi, what)
-        for b, n in enumerate(lengths):
-            if n == 0:
-                assert not out[b].any(), f"{what}: a sequence without keys is not all zeros"
+    CH.interval_case(*p)
+
+
+@pytest.mark.parametrize("p", R.NEG_PARAMS, ids=[R.param_id(p) for p in R.NEG_PARAMS])
+def test_chunked_cases_by_the_interval_rule_with_a_negative_alpha(p):
+    """the reference is the smallest score and a later chunk moves it down: the caps re-derived for the sign, then the interval rule"""
+    CH.interval_case(*p, sign=-1)
 
 
 def test_uniform_softmax_is_exact():
@@ -62,10 +53,32 @@ def test_uniform_softmax_is_exact():
 
 @pytest.mark.parametrize("i", range(len(R.ONE_HOT)))
 def test_one_hot_softmax_is_exact(i):
-    qn, kn, vn, lengths, alpha, ml, hot = R.one_hot_case(i)
-    q, k, v = _dev(qn, kn, vn)
-    for pv in (1.0 / 127, 0.003):
-        assert_bits_equal(_run(q, k, v, lengths, alpha, pv, ml), R.one_hot_expected(vn, hot, pv), f"one-hot {R.ONE_HOT[i]}, pv_alpha {pv}")
+    CH.one_hot(R.one_hot_case(i), f"one-hot {R.ONE_HOT[i]}")
+
+
+@pytest.mark.parametrize("i", range(len(R.ONE_HOT_R)), ids=[f"r{s[1]}" for s in R.ONE_HOT_R])
+def test_one_hot_at_every_r(i):
+    """rows t16 < r of the tile, the head mapping and the [r][chunk + 4] strip pitch at every r the entry takes"""
+    CH.one_hot(R.one_hot_r_case(i), f"one-hot {R.ONE_HOT_R[i]}")
+
+
+@pytest.mark.parametrize("i", range(len(R.ONE_HOT_D)), ids=[f"d{s[2]}" for s in R.ONE_HOT_D])
+def test_one_hot_at_every_head_dim(i):
+    """columns col < D of the last 64-column block, the addressing and the epilogue at every D the entry takes"""
+    CH.one_hot(R.one_hot_d_case(i), f"one-hot {R.ONE_HOT_D[i]}")
+
+
+@pytest.mark.parametrize("i", range(len(R.WALK)), ids=[f"kv{s[0]}x{s[1]}d{s[2]}" for s in R.WALK])
+def test_key_position_walk_is_exact(i):
+    """every key counted exactly once, at the seams: three chunks, sequence b's only weight at the b-th of walk_positions(); one launch per shape"""
+    CH.walk(i, 8)
+
+
+@pytest.mark.parametrize("neg", [False, True], ids=["max", "min"])
+@pytest.mark.parametrize("i", range(len(R.WALK)), ids=[f"kv{s[0]}x{s[1]}d{s[2]}" for s in R.WALK])
+def test_two_weights_in_different_chunks_are_exact(i, neg):
+    """the rescale of pass 1, exactly: 34 v[A] + 93 v[B] whichever chunk holds which, for the max reference and (-qk_alpha on negated keys) the min reference"""
+    CH.two_weights(i, neg)
 
 
 @pytest.mark.parametrize("case", [1, 3, 4])
@@ -82,6 +95,34 @@ def test_rows_behind_the_length_and_the_pitch_gap_do_not_matter(case):
         q, k, v = _dev(qn, k2, v2)
         outs.append(_run(q, k, v, lengths, R.qk_alpha(case, 1), R.PV_ALPHAS[0], ml))
     assert_bits_equal(outs[0], outs[1], f"case {case}: the output depends on rows >= n_b")
+
+
+@pytest.mark.parametrize("case", R.POISONED, ids=[R.param_id((c, 1)) for c in R.POISONED])
+def test_a_poisoned_tail_does_not_matter(case):
+    """every row at or beyond n_b, the rows between max_len and the pitch included, holds the key that would win a row outright and V of +-127; kv_len[0] is above
+    max_len, so the poison sits exactly at row max_len.  One stray key moves most outputs: bit-equal to the run with those rows zeroed, and inside the intervals"""
+    qn = R.operands(case)[0]
+    k2, v2, k0, v0, kv_len, n_b = R.poisoned(case)
+    ml, alpha, pv = R.max_len(R.CASES[case][3]), R.qk_alpha(case, 1), R.PV_ALPHAS[0]
+    n = torch.tensor(kv_len, dtype=torch.int32, device=DEV)
+    q, kp, vp, kz, vz = _dev(qn, k2, v2, k0, v0)
+    got = _run(q, kp, vp, None, alpha, pv, ml, kv_len=n)
+    assert_bits_equal(got, _run(q, kz, vz, None, alpha, pv, ml, kv_len=n), f"case {case}: the output depends on rows >= n_b")
+    s_lo, s_hi, nband, total = R.poisoned_sums(case)
+    lo, hi = R.interval(s_lo, s_hi, pv)
+    R.caps(lo, hi, nband, total, f"poisoned case {case}")
+    R.check(got, lo, hi, f"poisoned case {case}")
+
+
+@pytest.mark.parametrize("nw", [4, 16])
+def test_the_4_wave_and_16_wave_kernels_in_a_child_process(nw):
+    """ASQ_DECODE_WAVES is latched on first use: tests/attn_decode_child.py runs the walk for its own number of waves, the two weights and three interval cases in a
+    fresh process.  A child that ends by a signal or the time limit fails this test; nothing is tried again"""
+    env = dict(os.environ, ASQ_DECODE_WAVES=str(nw))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "attn_decode_child.py"), str(nw)], env=env, capture_output=True, text=True, timeout=300)
+    print(r.stdout[-6000:])
+    assert r.returncode == 0, f"the {nw}-wave child returned {r.returncode}: {r.stdout[-1500:]} {r.stderr[-1500:]}"
+    assert f"{nw} waves: all passed" in r.stdout
 
 
 def test_kv_len_variations_and_a_negative_alpha():

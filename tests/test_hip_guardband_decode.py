@@ -2,7 +2,8 @@
 
 asq_attn_decode_i8: q, both caches (as [B, max_len + 2 rows] regions: the pitch is wider than max_len rows) and kv_len are input regions, out an output region.  The
 raw call returns ASQ_OK, writes the bytes of the ordinary ops.attn_decode_i8 call, leaves every guard and every input as it was and gives the same bytes under both
-flank poisons.  kv_len holds entries above max_len and below 0: a kernel that trusted them would read a cache's flank.
+flank poisons.  kv_len holds entries above max_len and below 0: a kernel that trusted them would read a cache's flank.  The shapes take every ceil(D / 64) of 1 to 4,
+the one-pass and the chunked path.
 asq_rope_quantize_qkv_at: q, k, v as the three slices of one fused input region, the tables and pos as inputs, q8 and the two whole caches as outputs.  Every cache byte
 outside rows pos[b] .. pos[b] + S - 1 of sequence b stays at the arena's pattern, the written rows and q8 equal ops.rope_quantize_qkv called per sequence, and a token
 whose position is outside 0 .. min(T, Smax) - 1 writes no cache byte and a zero q8 row.
@@ -19,8 +20,10 @@ pytestmark = pytest.mark.gpu
 DECODE, APPEND = "asq_attn_decode_i8", "asq_rope_quantize_qkv_at"
 ALPHAS = (0.0009, 1.0 / 127)
 SCALES = (0.37, 0.11, 0.73)
-# (B, Hq, Hkv, D, max_len, kv_len): the last is chunked (16 rows: 1024 keys per chunk) with a head_dim that is no multiple of 64
-DECODE_SHAPES = [(2, 4, 2, 64, 40, [49, 17]), (3, 8, 1, 128, 1100, [1100, -3, 1029]), (1, 16, 1, 80, 1300, [1 << 30]), (4, 2, 2, 16, 1, [1, 0, 5, 1])]
+# (B, Hq, Hkv, D, max_len, kv_len): the third is chunked (16 rows: 1024 keys per chunk) with a head_dim that is no multiple of 64; the last two are the wide head dims,
+# ceil(D / 64) = 3 (r = 3) and 4, the second of them chunked
+DECODE_SHAPES = [(2, 4, 2, 64, 40, [49, 17]), (3, 8, 1, 128, 1100, [1100, -3, 1029]), (1, 16, 1, 80, 1300, [1 << 30]), (4, 2, 2, 16, 1, [1, 0, 5, 1]),
+                 (2, 6, 2, 192, 70, [70, 33]), (1, 16, 1, 256, 1100, [1100])]
 # (B, S, Hq, Hkv, D, Smax, T, pos): positions per sequence; -1, 100 and a slot that crosses min(T, Smax) are out of range in part or in whole
 APPEND_SHAPES = [(1, 1, 1, 1, 16, 4, 6, [0]), (3, 1, 8, 2, 128, 9, 12, [8, 0, 5]), (4, 5, 4, 4, 64, 16, 14, [3, -1, 11, 100]), (2, 67, 5, 1, 48, 80, 90, [13, 0])]
 ARENA_BYTES = 64 << 20
