@@ -1,4 +1,4 @@
-"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h and include/asq_hip_decode.h)."""
+"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h, include/asq_hip_decode.h and include/asq_hip_paged.h)."""
 import ctypes
 import os
 import threading
@@ -114,6 +114,14 @@ DECODE_SIGNATURES = {
                                         _vp]),
 }
 
+# include/asq_hip_paged.h: the same decode step on paged caches (pools of fixed-size pages behind a block table), a fourth table: DECODE_SIGNATURES is tied to its
+# guard-band file like ATTN_SIGNATURES; probed by presence, ASQ_VERSION stays
+PAGED_SIGNATURES = {
+    "asq_attn_decode_i8_paged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
+    "asq_rope_quantize_qkv_paged": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32,
+                                           _i64, _i64, _i64, _i64, _i64, _vp]),
+}
+
 
 def lib():
     """Load libasq_hip.so once.  Fails loudly: there is no fallback implementation."""
@@ -132,7 +140,7 @@ def lib():
                 # imported torch).  The host side above the C-ABI is torch plumbing anyway (ops.py).
                 import torch  # noqa: F401
                 h = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()) + list(PAGED_SIGNATURES.items()):
                     fn = getattr(h, name)  # AttributeError if the .so lacks a declared symbol
                     fn.restype, fn.argtypes = res, args
                 if h.asq_version() != ASQ_VERSION:   # a stale build: argument lists and the workspace contract may differ

@@ -18,6 +18,7 @@
 // No workgroup waits for another, no workspace, no float atomics.  Rows >= n of the cache are never read (load16_guarded / load4_kn against n).
 #include "asq_bmm_core.h"
 #include "../../include/asq_hip_decode.h"
+#include "../../include/asq_hip_paged.h"
 
 namespace asq {
 
@@ -44,8 +45,19 @@ struct DecArgs {
     float qk_alpha, pv_alpha;
 };
 
+// asq_attn_decode_i8_paged (include/asq_hip_paged.h): k / v are the pools' bases and `pitch` the bytes between pages; key n of sequence b is row n % page_size of
+// page table[b * table_pitch + n / page_size]
+struct DecPagedArgs : DecArgs {
+    const int32_t *table;
+    int64_t table_pitch;
+    int num_pages, page_size;
+};
+
 // ND: 64-byte steps of D (ceil(D / 64)); NW: waves
-template <int ND, int NW> __global__ void __launch_bounds__(64 * NW) attn_decode_i8_kernel(const DecArgs A)
+// PAGED: the caches are pools of pages behind a block table.  A template flag for GROUPED's reason (asq_bmm.hip): the instantiations without it take DecArgs and
+// compile to what they were.  The one new thing is where a 16-row group of keys starts (page_size % 16 == 0: the 16 keys of a score tile and a lane's 16 V rows lie
+// inside one page); the chunk, the tile -> wave assignment, the strip, the loaders and the merge order are shared, so every output byte is the contiguous form's.
+template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(64 * NW) attn_decode_i8_kernel(const std::conditional_t<PAGED, DecPagedArgs, DecArgs> A)
 {
     extern __shared__ __attribute__((aligned(16))) char dec_lds[];
     constexpr int NT = 64 * NW;
@@ -58,7 +70,8 @@ template <int ND, int NW> __global__ void __launch_bounds__(64 * NW) attn_decode
     int nb = A.kv_len ? A.kv_len[b] : A.max_len;
     nb = nb < 0 ? 0 : (nb > A.max_len ? A.max_len : nb);
     const int64_t ld = (int64_t)A.Hkv * D, qoff = ((int64_t)b * A.Hq + (int64_t)g * r) * D;   // the group's r heads are r * D contiguous bytes of q and out
-    const int8_t *const qb = A.q + qoff, *const kb = A.k + b * A.pitch + (int64_t)g * D, *const vb = A.v + b * A.pitch + (int64_t)g * D;
+    const int64_t seq = PAGED ? 0 : b * A.pitch;   // (PAGED: the page's offset comes per 16-row group, group_at)
+    const int8_t *const qb = A.q + qoff, *const kb = A.k + seq + (int64_t)g * D, *const vb = A.v + seq + (int64_t)g * D;
     int8_t *const ob = A.out + qoff;
     if (nb == 0) {   // (the whole workgroup: no barrier has been met)
         for (int i = tid; i < r * D / 16; i += NT) *(v4i *)(ob + i * 16) = (v4i){0, 0, 0, 0};
@@ -73,6 +86,19 @@ template <int ND, int NW> __global__ void __launch_bounds__(64 * NW) attn_decode
     for (int i = tid; i < 16 * NW; i += NT) part[i] = 0.0f;
     if (tid < 16) rowref[tid] = ref0;
 
+    // PAGED: keys n .. n + 15 (n % 16 == 0) -> the byte offset of key n's row from kb / vb.  live: the group holds a key below the sequence's length -- only then is
+    // the table read, so no entry at or behind ceil(n_b / page_size) ever is; the page id is clamped, so no table content leads outside the pools.
+    [[maybe_unused]] auto group_at = [&](int n, bool live) -> int64_t {
+        if constexpr (PAGED) {
+            const uint32_t pg = (uint32_t)n / (uint32_t)A.page_size, row = (uint32_t)n - pg * (uint32_t)A.page_size;
+            int id = live ? A.table[b * A.table_pitch + pg] : 0;
+            id = id < 0 ? 0 : (id >= A.num_pages ? A.num_pages - 1 : id);
+            return id * A.pitch + (int64_t)row * ld;
+        } else {
+            return (int64_t)n * ld;
+        }
+    };
+
     v4i fq[ND];   // row t16 of the group's q, 16 bytes at 16 q16 of each 64-byte step
 #pragma unroll
     for (int ds = 0; ds < ND; ++ds) fq[ds] = load16_guarded(qb, D, t16, r, ds * 64 + q16 * 16, D, true);
@@ -84,10 +110,23 @@ template <int ND, int NW> __global__ void __launch_bounds__(64 * NW) attn_decode
         int tm = ref0;
         for (int kt0 = wave; kt0 < tiles; kt0 += 4 * NW) {
             v4i fk[4][ND];
+            [[maybe_unused]] int64_t koff[4];   // PAGED: the four tiles' page lookups (uniform over the wave: scalar loads), issued ahead of the K loads that need them
+            [[maybe_unused]] int left[4];       //        and the keys of the chunk from each tile's first on
+            if constexpr (PAGED) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int n = __builtin_amdgcn_readfirstlane(n0 + (kt0 + u * NW) * 16);
+                    left[u] = n0 + cn - n;
+                    koff[u] = group_at(n, left[u] > 0);
+                }
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
-                for (int ds = 0; ds < ND; ++ds) fk[u][ds] = load16_guarded(kb, ld, n0 + (kt0 + u * NW) * 16 + t16, n0 + cn, ds * 64 + q16 * 16, D, true);
+                for (int ds = 0; ds < ND; ++ds) {
+                    if constexpr (PAGED) fk[u][ds] = load16_guarded(kb + koff[u], ld, t16, left[u], ds * 64 + q16 * 16, D, true);
+                    else fk[u][ds] = load16_guarded(kb, ld, n0 + (kt0 + u * NW) * 16 + t16, n0 + cn, ds * 64 + q16 * 16, D, true);
+                }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int kt = kt0 + u * NW;
@@ -170,10 +209,15 @@ template <int ND, int NW> __global__ void __launch_bounds__(64 * NW) attn_decode
         for (int ks = wave; ks * 64 < cn; ks += NW) {
             const int key = ks * 64 + q16 * 16;   // the lane's 16 keys, chunk-relative
             uint32_t rows[ND][16];
+            [[maybe_unused]] const int8_t *vp = vb;   // PAGED: the lane's 16 V rows lie in one page, one lookup per quarter wave
+            if constexpr (PAGED) vp = vb + group_at(n0 + key, key < cn);
 #pragma unroll
             for (int cb = 0; cb < ND; ++cb)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) rows[cb][i] = load4_kn(vb, ld, D, n0 + key + i, n0 + cn, cb * 64 + 4 * t16, true);
+                for (int i = 0; i < 16; ++i) {
+                    if constexpr (PAGED) rows[cb][i] = load4_kn(vp, ld, D, i, cn - key, cb * 64 + 4 * t16, true);
+                    else rows[cb][i] = load4_kn(vb, ld, D, n0 + key + i, n0 + cn, cb * 64 + 4 * t16, true);
+                }
             v4i fp = (v4i){0, 0, 0, 0};
             if (t16 < r && key < cn) {
 #pragma unroll
@@ -242,15 +286,15 @@ static int dec_waves()
     return nw;
 }
 
-template <int ND> static int launch_decode(const DecArgs &a, int64_t grid, hipStream_t s)
+template <int ND, bool PAGED = false> static int launch_decode(const std::conditional_t<PAGED, DecPagedArgs, DecArgs> &a, int64_t grid, hipStream_t s)
 {
     const int nw = ND > 2 && dec_waves() == 16 ? 8 : dec_waves();   // D > 128 at 16 waves (128 VGPRs) would spill: not instantiated
     const size_t lds = (size_t)dec_lds_bytes(a.r, a.chunk, ND, nw);
-    const char *const what = "asq_attn_decode_i8";
-    if (nw == 4) return launch_lds(what, attn_decode_i8_kernel<ND, 4>, DEC_LDS_MAX, lds, grid, 256, s, a);
+    const char *const what = PAGED ? "asq_attn_decode_i8_paged" : "asq_attn_decode_i8";
+    if (nw == 4) return launch_lds(what, attn_decode_i8_kernel<ND, 4, PAGED>, DEC_LDS_MAX, lds, grid, 256, s, a);
     if constexpr (ND <= 2)
-        if (nw == 16) return launch_lds(what, attn_decode_i8_kernel<ND, 16>, DEC_LDS_MAX, lds, grid, 1024, s, a);
-    return launch_lds(what, attn_decode_i8_kernel<ND, 8>, DEC_LDS_MAX, lds, grid, 512, s, a);
+        if (nw == 16) return launch_lds(what, attn_decode_i8_kernel<ND, 16, PAGED>, DEC_LDS_MAX, lds, grid, 1024, s, a);
+    return launch_lds(what, attn_decode_i8_kernel<ND, 8, PAGED>, DEC_LDS_MAX, lds, grid, 512, s, a);
 }
 
 }  // namespace asq
@@ -284,4 +328,46 @@ extern "C" int asq_attn_decode_i8(const int8_t *q, const int8_t *k_cache, const 
     default: rc = launch_decode<4>(a, grid, st); break;
     }
     return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_decode_i8");
+}
+
+extern "C" int asq_attn_decode_i8_paged(const int8_t *q, const int8_t *k_pool, const int8_t *v_pool, const int32_t *block_table, const int32_t *kv_len, int8_t *out, int64_t B,
+                                        int64_t Hq, int64_t Hkv, int64_t D, int64_t num_pages, int64_t page_size, int64_t page_pitch, int64_t table_pitch, int64_t max_len,
+                                        float qk_alpha, float pv_alpha, void *stream)
+{
+    const AsqRange range_("asq_attn_decode_i8_paged");
+    const int64_t lim = 1ll << 31;
+    ASQ_REQUIRE(B >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17) && num_pages >= 0 &&
+                    num_pages < lim && page_size >= 0 && page_size < lim && table_pitch >= 0 && table_pitch < lim,
+                ASQ_ERR_DIM, "asq_attn_decode_i8_paged: bad dims B=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld num_pages=%lld page_size=%lld table_pitch=%lld", (long long)B,
+                (long long)Hq, (long long)Hkv, (long long)D, (long long)max_len, (long long)num_pages, (long long)page_size, (long long)table_pitch);
+    int64_t grid = 0, qn = 0, page = 0;   // as asq_attn_decode_i8; a page holds page_size * Hkv * D bytes
+    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &grid) && grid < lim && !__builtin_mul_overflow(B * Hq, D, &qn) && !__builtin_mul_overflow(page_size * Hkv, D, &page) &&
+                    page <= (1ll << 60),
+                ASQ_ERR_DIM, "asq_attn_decode_i8_paged: dims overflow");
+    if (B == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(q && k_pool && v_pool && block_table && out, ASQ_ERR_NULL, "asq_attn_decode_i8_paged: NULL pointer");
+    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM,
+                "asq_attn_decode_i8_paged: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)", (long long)Hq, (long long)Hkv, (long long)D);
+    const int64_t pp = page_pitch == 0 ? page : page_pitch;
+    ASQ_REQUIRE(page_size > 0 && page_size % 16 == 0, ASQ_ERR_DIM, "asq_attn_decode_i8_paged: page_size must be a positive multiple of 16, got %lld", (long long)page_size);
+    ASQ_REQUIRE(pp >= page && pp % 16 == 0 && pp <= (1ll << 60) / (num_pages > 0 ? num_pages : 1), ASQ_ERR_DIM,
+                "asq_attn_decode_i8_paged: page_pitch must be 0 (dense) or >= page_size * Hkv * D and a multiple of 16");
+    ASQ_REQUIRE(max_len <= table_pitch * page_size, ASQ_ERR_DIM, "asq_attn_decode_i8_paged: max_len %lld needs more than the %lld table entries of %lld keys a sequence has",
+                (long long)max_len, (long long)table_pitch, (long long)page_size);
+    ASQ_REQUIRE(max_len == 0 || num_pages > 0, ASQ_ERR_DIM, "asq_attn_decode_i8_paged: max_len %lld with a pool of no pages", (long long)max_len);
+    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_pool) | ((uintptr_t)v_pool) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN,
+                "asq_attn_decode_i8_paged: q, the pools and out must be 16-B aligned");
+    ASQ_REQUIRE((((uintptr_t)kv_len | (uintptr_t)block_table) & 3) == 0, ASQ_ERR_ALIGN, "asq_attn_decode_i8_paged: kv_len and block_table must be 4-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int r = (int)(Hq / Hkv);
+    const DecPagedArgs a{{q, k_pool, v_pool, kv_len, out, pp, (int)Hq, (int)Hkv, (int)D, r, (int)max_len, dec_chunk(r, max_len), qk_alpha, pv_alpha},
+                         block_table, table_pitch, (int)num_pages, (int)page_size};
+    int rc;
+    switch ((D + 63) / 64) {
+    case 1: rc = launch_decode<1, true>(a, grid, st); break;
+    case 2: rc = launch_decode<2, true>(a, grid, st); break;
+    case 3: rc = launch_decode<3, true>(a, grid, st); break;
+    default: rc = launch_decode<4, true>(a, grid, st); break;
+    }
+    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_decode_i8_paged");
 }

@@ -16,6 +16,7 @@
 #include "asq_rope_core.h"
 #include "../../include/asq_hip_attn.h"
 #include "../../include/asq_hip_decode.h"
+#include "../../include/asq_hip_paged.h"
 
 namespace asq {
 
@@ -36,6 +37,14 @@ struct RopeQ8AtArgs : RopeQ8Args {
     int64_t lim;
 };
 
+// asq_rope_quantize_qkv_paged (include/asq_hip_paged.h): k8 / v8 are the pools' bases, kv_batch_pitch the bytes between pages; position p of sequence b is row
+// p % page_size of page table[b * table_pitch + p / page_size]
+struct RopeQ8PagedArgs : RopeQ8AtArgs {
+    const int32_t *table;
+    int64_t table_pitch;
+    int num_pages, page_size;
+};
+
 template <int DT> __device__ __forceinline__ void quant_div_vec(const v4i &w, float s, float y, uint32_t (&o)[2])
 {
     if (y != 0.0f) quant_vec<DT>(w, QDivFast<DT>{s, y}, o);
@@ -51,8 +60,12 @@ template <int DT> __device__ __forceinline__ void store_q8(int8_t *p, const uint
 // IDX: uint32_t when nwork fits (every model-sized call), so that the three divisions by run-time values are 32-bit ones
 // AT: token (b, s) sits at position pos[b] + s (table row and cache row); a token outside 0 .. lim - 1 writes no cache byte, reads no table row and zeroes its
 // q8 row.  A template flag for GROUPED's reason (asq_bmm.hip): the instantiations without it take RopeQ8Args and compile to what they were.
-template <int DT, class IDX, bool AT = false> __global__ void __launch_bounds__(256) rope_q8_kernel(const std::conditional_t<AT, RopeQ8AtArgs, RopeQ8Args> A)
+// PAGED (with AT): the token's cache row is row (pos[b] + s) % page_size of the page its table entry names -- one table read per token; an entry outside
+// 0 .. num_pages - 1 skips the token like a position out of range.  The same rule: the instantiations without the flag are what they were.
+template <int DT, class IDX, bool AT = false, bool PAGED = false>
+__global__ void __launch_bounds__(256) rope_q8_kernel(const std::conditional_t<PAGED, RopeQ8PagedArgs, std::conditional_t<AT, RopeQ8AtArgs, RopeQ8Args>> A)
 {
+    static_assert(AT || !PAGED, "the paged append reads its positions on the device");
     constexpr int VEC = ElemT<DT>::VEC;
     constexpr int ES = 16 / VEC;   // bytes per element
     const IDX idx = (IDX)blockIdx.x * 256 + threadIdx.x;
@@ -67,10 +80,20 @@ template <int DT, class IDX, bool AT = false> __global__ void __launch_bounds__(
     const bool is_q = ht < A.Hq, is_k = !is_q && ht < A.Hq + A.Hkv;
     const int h = is_q ? ht : (is_k ? ht - A.Hq : ht - A.Hq - A.Hkv);
     int64_t crow = s;   // the token's row from k8 / v8; AT: in the tables too
+    [[maybe_unused]] int64_t slab = b, srow = s;   // PAGED: the page and the row in it that hold the token
     if constexpr (AT) {
         const int64_t p = A.pos[b];
         crow = p + s;
-        if (p < 0 || crow >= A.lim) {
+        bool skip = p < 0 || crow >= A.lim;
+        if constexpr (PAGED) {
+            if (!skip) {   // (crow < lim <= table_pitch * page_size: the entry exists)
+                const int64_t pg = crow / A.page_size;
+                slab = A.table[b * A.table_pitch + pg];
+                srow = crow - pg * A.page_size;
+                skip = slab < 0 || slab >= A.num_pages;
+            }
+        }
+        if (skip) {
             if (is_q) {
                 int8_t *z = A.q8 + (bs * A.Hq + h) * D + c * VEC;
                 const uint32_t zero[2] = {0, 0};
@@ -82,7 +105,7 @@ template <int DT, class IDX, bool AT = false> __global__ void __launch_bounds__(
     }
     const int64_t in_row = bs * (is_q ? A.q_pitch : (is_k ? A.k_pitch : A.v_pitch));
     const char *x = (is_q ? A.q : (is_k ? A.k : A.v)) + (in_row + (int64_t)h * D + (int64_t)c * VEC) * ES;
-    int8_t *o = is_q ? A.q8 + (bs * A.Hq + h) * D : (is_k ? A.k8 : A.v8) + b * A.kv_batch_pitch + (crow * A.Hkv + h) * D;
+    int8_t *o = is_q ? A.q8 + (bs * A.Hq + h) * D : (is_k ? A.k8 : A.v8) + (PAGED ? slab : b) * A.kv_batch_pitch + ((PAGED ? srow : crow) * A.Hkv + h) * D;
     o += c * VEC;
     const float qs = is_q ? A.q_s : (is_k ? A.k_s : A.v_s), qy = is_q ? A.q_y : (is_k ? A.k_y : A.v_y);
     const int64_t half_bytes = (int64_t)(D / 2) * ES;
@@ -112,6 +135,13 @@ template <int DT> static void launch_rope_q8_at(const RopeQ8AtArgs &a, hipStream
     const unsigned blocks = (unsigned)((a.nwork + 255) / 256);
     if (a.nwork + 255 < (1ll << 32)) hipLaunchKernelGGL((rope_q8_kernel<DT, uint32_t, true>), dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((rope_q8_kernel<DT, uint64_t, true>), dim3(blocks), dim3(256), 0, s, a);
+}
+
+template <int DT> static void launch_rope_q8_paged(const RopeQ8PagedArgs &a, hipStream_t s)
+{
+    const unsigned blocks = (unsigned)((a.nwork + 255) / 256);
+    if (a.nwork + 255 < (1ll << 32)) hipLaunchKernelGGL((rope_q8_kernel<DT, uint32_t, true, true>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((rope_q8_kernel<DT, uint64_t, true, true>), dim3(blocks), dim3(256), 0, s, a);
 }
 
 }  // namespace asq
@@ -188,4 +218,48 @@ extern "C" int asq_rope_quantize_qkv_at(const void *q, const void *k, const void
                          pos, tab_rows < max_len ? tab_rows : max_len};
     asq_dispatch_dt(x_dtype, [&](auto dt) { launch_rope_q8_at<decltype(dt)::value>(a, st); });
     return asq_after_launch(st, "asq_rope_quantize_qkv_at");
+}
+
+extern "C" int asq_rope_quantize_qkv_paged(const void *q, const void *k, const void *v, int64_t q_pitch, int64_t k_pitch, int64_t v_pitch, int x_dtype, const void *cos_tab,
+                                           const void *sin_tab, int64_t tab_rows, const int32_t *pos, const int32_t *block_table, int8_t *q8, int8_t *k_pool, int8_t *v_pool,
+                                           int64_t num_pages, int64_t page_size, int64_t page_pitch, int64_t table_pitch, int64_t max_len, float q_scale, float k_scale,
+                                           float v_scale, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D, void *stream)
+{
+    const AsqRange range_("asq_rope_quantize_qkv_paged");
+    const int64_t lim = 1ll << 31;
+    ASQ_REQUIRE(B >= 0 && S >= 0 && Hq >= 0 && Hkv >= 0 && D > 0 && B < lim && S < lim && Hq < lim && Hkv < lim && Hq + 2 * Hkv < lim && D < (1ll << 20) && tab_rows >= 0 &&
+                    tab_rows < (1ll << 40) && max_len >= 0 && max_len < lim && num_pages >= 0 && num_pages < lim && page_size >= 0 && page_size < lim && table_pitch >= 0 &&
+                    table_pitch < lim,
+                ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: bad dims");
+    int64_t heads = 0, nelem = 0, page = 0;   // as asq_rope_quantize_qkv; a page holds page_size * Hkv * D bytes
+    ASQ_REQUIRE(!__builtin_mul_overflow(B * S, Hq + 2 * Hkv, &heads) && !__builtin_mul_overflow(heads, D, &nelem) && nelem < (1ll << 41) &&
+                    !__builtin_mul_overflow(page_size * Hkv, D, &page) && page <= (1ll << 60),
+                ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: dims overflow");
+    ASQ_REQUIRE(x_dtype == ASQ_F32 || x_dtype == ASQ_F16 || x_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_rope_quantize_qkv_paged: bad x_dtype %d", x_dtype);
+    if (B == 0 || S == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(q && k && v && cos_tab && sin_tab && pos && block_table && q8 && k_pool && v_pool, ASQ_ERR_NULL, "asq_rope_quantize_qkv_paged: NULL pointer");
+    const int vec = x_dtype == ASQ_F32 ? 4 : 8;
+    ASQ_REQUIRE(D % (2 * vec) == 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: head_dim must be a multiple of %d", 2 * vec);
+    const int64_t qld = q_pitch == 0 ? Hq * D : q_pitch, kld = k_pitch == 0 ? Hkv * D : k_pitch, vld = v_pitch == 0 ? Hkv * D : v_pitch;
+    ASQ_REQUIRE(qld >= Hq * D && kld >= Hkv * D && vld >= Hkv * D && qld % vec == 0 && kld % vec == 0 && vld % vec == 0 &&
+                    (qld > kld ? (qld > vld ? qld : vld) : (kld > vld ? kld : vld)) <= (1ll << 60) / (B * S),
+                ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: a row pitch must be 0 (dense) or >= H * D and a multiple of %d elements", vec);
+    const int64_t pp = page_pitch == 0 ? page : page_pitch;
+    ASQ_REQUIRE(page_size > 0 && page_size % 16 == 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: page_size must be a positive multiple of 16, got %lld", (long long)page_size);
+    ASQ_REQUIRE(pp >= page && pp % 16 == 0 && pp <= (1ll << 60) / (num_pages > 0 ? num_pages : 1), ASQ_ERR_DIM,
+                "asq_rope_quantize_qkv_paged: page_pitch must be 0 (dense) or >= page_size * Hkv * D and a multiple of 16");
+    ASQ_REQUIRE(max_len <= table_pitch * page_size, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: max_len %lld needs more than the %lld table entries of %lld rows a sequence has",
+                (long long)max_len, (long long)table_pitch, (long long)page_size);
+    ASQ_REQUIRE(max_len == 0 || num_pages > 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: max_len %lld with a pool of no pages", (long long)max_len);
+    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)cos_tab) | ((uintptr_t)sin_tab) | ((uintptr_t)q8) | ((uintptr_t)k_pool) | ((uintptr_t)v_pool)) & 15) == 0,
+                ASQ_ERR_ALIGN, "asq_rope_quantize_qkv_paged: pointers must be 16-B aligned");
+    ASQ_REQUIRE((((uintptr_t)pos | (uintptr_t)block_table) & 3) == 0, ASQ_ERR_ALIGN, "asq_rope_quantize_qkv_paged: pos and block_table must be 4-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const auto recip = [](float s) { return s > 0x1p-60f && s < 0x1p60f ? 1.0f / s : 0.0f; };   // asq_rope_quantize_qkv's choice
+    const RopeQ8PagedArgs a{{{(const char *)q, (const char *)k, (const char *)v, (const char *)cos_tab, (const char *)sin_tab, q8, k_pool, v_pool, qld, kld, vld, pp, 0,
+                              heads * (D / 2 / vec), q_scale, recip(q_scale), k_scale, recip(k_scale), v_scale, recip(v_scale), (int)S, (int)Hq, (int)Hkv, (int)D},
+                             pos, tab_rows < max_len ? tab_rows : max_len},
+                            block_table, table_pitch, (int)num_pages, (int)page_size};
+    asq_dispatch_dt(x_dtype, [&](auto dt) { launch_rope_q8_paged<decltype(dt)::value>(a, st); });
+    return asq_after_launch(st, "asq_rope_quantize_qkv_paged");
 }

@@ -15,7 +15,10 @@ What feeds it for a RoPE model (LLaMA, Mixtral, Baichuan-7B) is RopeQuantQKV: ro
 Int8KVCache in one launch (ops.rope_quantize_qkv), straight from the q/k/v projections' [B, S, H, d] outputs into the operands of layout="bshd".
 
 A batch of sequences of different lengths takes a decode step in two launches: RopeQuantQKV with a RaggedInt8KVCache appends one token per sequence at its own
-position (ops.rope_quantize_qkv_at), Int8Attention.decode attends over each sequence's own number of keys on the cache where it lies (ops.attn_decode_i8)."""
+position (ops.rope_quantize_qkv_at), Int8Attention.decode attends over each sequence's own number of keys on the cache where it lies (ops.attn_decode_i8).
+
+The same step on a paged cache -- fixed-size pages handed out from one pool, a block table per sequence, what a vLLM-style server keeps -- is RopeQuantQKV with a
+PagedInt8KVCache (ops.rope_quantize_qkv_paged) and Int8Attention.decode_paged (ops.attn_decode_i8_paged): the same two launches, the same bytes."""
 import torch
 
 from ... import ops
@@ -114,6 +117,15 @@ class Int8Attention(torch.nn.Module):
         return ops.attn_decode_i8(q8, k_cache, v_cache, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), max_len=max_len)
 
 
+    def decode_paged(self, q8, k_pool, v_pool, block_table, kv_len=None, max_len=None):
+        """decode on a paged cache, ONE launch (ops.attn_decode_i8_paged): q8 int8 [B, 1, Hq, d] -> [B, 1, Hq, d] over k_pool / v_pool [num_pages, page_size, Hkv, d]
+        (a PagedInt8KVCache's k and v), key n of sequence b in page block_table[b, n // page_size] (int32 [B, T] on the device).  kv_len and max_len as in decode
+        (max_len: T * page_size when absent).  The output bytes are decode's on a contiguous cache holding the same keys."""
+        if not torch.is_tensor(q8) or q8.dim() != 4 or q8.shape[1] != 1:
+            raise ValueError(f"q8 must be [B, 1, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        return ops.attn_decode_i8_paged(q8, k_pool, v_pool, block_table, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), max_len=max_len)
+
+
 class Int8KVCache:
     """A preallocated int8 KV cache in the token-major layout: k and v [B, Smax, Hkv, d] and the number of tokens held, `length` (one position for the whole batch).
     Plain tensor bookkeeping, on any device: slot(S) -> the views k[:, length:length + S], v[...] that the next S tokens are written into (ValueError past
@@ -189,6 +201,93 @@ class RaggedInt8KVCache:
         return max(self.lengths, default=0)
 
 
+class PagedInt8KVCache:
+    """A paged int8 KV cache: pools k and v [num_pages, page_size, Hkv, d] (page_size a multiple of 16), `block_table` int32 [batch, ceil(max_len / page_size)] and
+    `kv_len` int32 [batch] on the cache's device -- what ops.rope_quantize_qkv_paged and ops.attn_decode_i8_paged read; both are allocated once and only written in
+    place, so a captured step keeps reading the same addresses -- and their host mirrors: `lengths`, the page list of every sequence `pages`, and the free list `free`
+    (pages are handed out in ascending order at first, a freed page is the next one reused).  Memory follows the real lengths: a sequence holds ceil(n / page_size)
+    pages once reserve() has covered its n tokens.
+    reserve(S): the pages the next S tokens (an int, or one per sequence) need, taken from the free list and written into the table; ValueError before anything is
+    touched when the pool or max_len does not suffice.  advance(S): lengths += S within what is reserved.  reset(b=None): every sequence, or sequence b, back to 0,
+    its pages back to the free list (it forgets, it does not clear; stale table entries stay behind the length, where no kernel reads them).  bound() = max(lengths).
+    gather(b) -> sequence b's keys and values as contiguous [n_b, Hkv, d] tensors by plain torch indexing: for tests, and for a chunked prefill through
+    Int8Attention.forward(layout="bshd").  A refused call changes no state."""
+
+    def __init__(self, num_pages, page_size, kv_heads, head_dim, batch, max_len, device=None):
+        if num_pages < 0 or page_size <= 0 or page_size % 16 or batch < 0 or max_len < 0:
+            raise ValueError(f"PagedInt8KVCache: {num_pages} pages of {page_size} rows (a positive multiple of 16) for {batch} sequences of max_len {max_len}")
+        self.k = torch.zeros((num_pages, page_size, kv_heads, head_dim), dtype=torch.int8, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.block_table = torch.zeros((batch, -(-max_len // page_size)), dtype=torch.int32, device=device)
+        self.kv_len = torch.zeros((batch,), dtype=torch.int32, device=device)
+        self.max_len = max_len
+        self.lengths = [0] * batch
+        self.pages = [[] for _ in range(batch)]
+        self.free = list(range(num_pages - 1, -1, -1))   # a stack: pop() hands out page 0 first, a freed page next
+
+    @property
+    def page_size(self):
+        return self.k.shape[1]
+
+    def _steps(self, S, what):
+        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
+        if len(steps) != len(self.lengths) or any(s < 0 or n + s > self.max_len for s, n in zip(steps, self.lengths)):
+            raise ValueError(f"PagedInt8KVCache.{what}: {steps} more tokens after {self.lengths} do not fit {len(self.lengths)} sequences of max_len {self.max_len}")
+        return steps
+
+    def reserve(self, S):
+        steps = self._steps(S, "reserve")
+        need = [max(0, -(-(n + s) // self.page_size) - len(pg)) for n, s, pg in zip(self.lengths, steps, self.pages)]
+        if sum(need) > len(self.free):
+            raise ValueError(f"PagedInt8KVCache.reserve: {steps} more tokens after {self.lengths} need {sum(need)} more pages, {len(self.free)} are free")
+        rows, cols, ids = [], [], []
+        for b, m in enumerate(need):
+            for _ in range(m):
+                rows.append(b), cols.append(len(self.pages[b])), ids.append(self.free.pop())
+                self.pages[b].append(ids[-1])
+        if ids:   # one stream-ordered scatter of the changed entries
+            dev = self.block_table.device
+            self.block_table.index_put_((torch.tensor(rows).to(dev, non_blocking=True), torch.tensor(cols).to(dev, non_blocking=True)),
+                                        torch.tensor(ids, dtype=torch.int32).to(dev, non_blocking=True))
+
+    def _unreserve(self, held):
+        """give back, newest first, the pages beyond held[b] per sequence: the free list is what it was before the reserve() that took them (their table entries stay,
+        behind the lengths)"""
+        for pg, m in zip(reversed(self.pages), reversed(held)):
+            while len(pg) > m:
+                self.free.append(pg.pop())
+
+    def advance(self, S):
+        steps = self._steps(S, "advance")
+        if any(n + s > len(pg) * self.page_size for n, s, pg in zip(self.lengths, steps, self.pages)):
+            raise ValueError(f"PagedInt8KVCache.advance: {steps} more tokens after {self.lengths} go beyond the reserved pages {[len(pg) for pg in self.pages]}")
+        if isinstance(S, int):
+            self.kv_len.add_(S)
+        else:
+            self.kv_len.add_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
+        self.lengths = [n + s for n, s in zip(self.lengths, steps)]
+
+    def reset(self, b=None):
+        if b is None:
+            self.kv_len.zero_()
+            seqs = range(len(self.lengths))
+        else:
+            b = range(len(self.lengths))[b]   # (IndexError outside, a negative index counts from the end)
+            self.kv_len[b:b + 1].zero_()
+            seqs = (b,)
+        for i in seqs:
+            self.free.extend(reversed(self.pages[i]))
+            self.pages[i], self.lengths[i] = [], 0
+
+    def bound(self):
+        return max(self.lengths, default=0)
+
+    def gather(self, b):
+        n = self.lengths[b]
+        idx = torch.tensor(self.pages[b][:-(-n // self.page_size)], dtype=torch.long).to(self.k.device)
+        return self.k[idx].flatten(0, 1)[:n].contiguous(), self.v[idx].flatten(0, 1)[:n].contiguous()
+
+
 class RopeQuantQKV(torch.nn.Module):
     """Rotary embedding of q and k, the static per-tensor int8 quantisers of q, k and v (x / scale in x's dtype, round, clamp) and the KV-cache append as ONE launch
     (ops.rope_quantize_qkv): every byte is what ops.rope followed by ops.quantize_act(., "per-tensor-div", scale) gives.  The state dict is the three scalar buffers
@@ -205,7 +304,11 @@ class RopeQuantQKV(torch.nn.Module):
     With a RaggedInt8KVCache (B >= 1 sequences of different lengths) token (b, s) sits at position cache.kv_len[b] + s, read on the device (ops.rope_quantize_qkv_at; `pos`
     is not used); the cache then advances by `advance` -- S tokens per sequence when absent, an int or B ints otherwise -- and the call returns (q8, cache.k, cache.v),
     the whole caches, which Int8Attention.decode(q8, cache.k, cache.v, cache.kv_len) reads in place.  A padded prefill is one call on a fresh cache with S = the longest
-    prompt and advance = the true lengths: the next appends overwrite the pad rows, which no decode step reads."""
+    prompt and advance = the true lengths: the next appends overwrite the pad rows, which no decode step reads.
+
+    With a PagedInt8KVCache the same, on pages: the cache reserves the pages the S written rows need (ValueError before anything is launched when the pool or max_len
+    does not suffice), the append goes through ops.rope_quantize_qkv_paged, the cache advances, and the call returns (q8, cache.k, cache.v), the pools, which
+    Int8Attention.decode_paged(q8, cache.k, cache.v, cache.block_table, cache.kv_len) reads in place."""
 
     _SCALES = ("q_scale", "k_scale", "v_scale")
 
@@ -239,6 +342,20 @@ class RopeQuantQKV(torch.nn.Module):
             cache._steps(S)                                     # the S written rows fit every sequence ...
             steps = cache._steps(S if advance is None else advance)   # ... and so does what the cache advances by (ValueError before anything is launched)
             q8, _, _ = ops.rope_quantize_qkv_at(q, k, v, cos, sin, qs, ks, vs, cache.kv_len, cache.k, cache.v)
+            cache.advance(S if advance is None else steps)
+            return q8, cache.k, cache.v
+        if isinstance(cache, PagedInt8KVCache):
+            cache._steps(S, "reserve")
+            steps = cache._steps(S if advance is None else advance, "advance")
+            if any(a > S for a in steps):
+                raise ValueError(f"PagedInt8KVCache: advance {steps} goes beyond the {S} rows written")
+            held = [len(pg) for pg in cache.pages]
+            cache.reserve(S)
+            try:
+                q8, _, _ = ops.rope_quantize_qkv_paged(q, k, v, cos, sin, qs, ks, vs, cache.kv_len, cache.block_table, cache.k, cache.v, max_len=cache.max_len)
+            except Exception:
+                cache._unreserve(held)   # a refused append keeps no page
+                raise
             cache.advance(S if advance is None else steps)
             return q8, cache.k, cache.v
         k_out, v_out = cache.slot(S)

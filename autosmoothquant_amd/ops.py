@@ -843,6 +843,85 @@ def attn_decode_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, max_len=None
     return out
 
 
+def _kv_pools(k_pool, v_pool, Hkv, D):
+    """k_pool / v_pool of the paged ops: two int8 [num_pages, page_size, Hkv, D] tensors of one shape with strides (pitch, Hkv * D, D, 1) and one pitch -- _kv_caches'
+    rule with pages in place of sequences -- and a page size that is a positive multiple of 16 -> (num_pages, page_size, Hkv, pitch; 0: dense)"""
+    num_pages = k_pool.shape[0] if isinstance(k_pool, torch.Tensor) and k_pool.dim() == 4 else 0
+    page_size, hkv, pitch = _kv_caches(k_pool, v_pool, num_pages, Hkv, D)
+    if page_size == 0 or page_size % 16:
+        raise ValueError(f"k_pool and v_pool must hold pages of a positive multiple of 16 rows, got {list(k_pool.shape)}")
+    return num_pages, page_size, hkv, pitch
+
+
+def _block_table(t, B):
+    """block_table of the paged ops: int32 [B, T] with row stride >= T and unit column stride (a table, or a [:, :T] view of a wider one) -> (T, the row stride)"""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or (t.shape[1] > 1 and t.stride(1) != 1)
+            or (B > 1 and t.stride(0) < t.shape[1])):
+        raise ValueError(f"block_table must be an int32 [{B}, T] tensor with row stride >= T and unit column stride, got {getattr(t, 'dtype', type(t))} "
+                         f"{list(getattr(t, 'shape', []))} with strides {t.stride() if isinstance(t, torch.Tensor) else None}")
+    return t.shape[1], (t.stride(0) if B > 1 else t.shape[1])
+
+
+def rope_quantize_qkv_paged(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, block_table, k_pool, v_pool, max_len=None):
+    """rope_quantize_qkv_at into paged caches (asq_rope_quantize_qkv_paged) -> (q8, k_pool, v_pool): token (b, s) is rotated with table row pos[b] + s and its k / v are
+    written to row (pos[b] + s) % page_size of page block_table[b, (pos[b] + s) // page_size]; S > 1 may cross page edges.  q, k, v, cos, sin, pos: rope_quantize_qkv_at's
+    rules.  k_pool / v_pool: int8 [num_pages, page_size, Hkv, D] of one shape with strides (pitch, Hkv * D, D, 1) and one pitch, page_size a multiple of 16.  block_table:
+    int32 [B, T] on the device, row stride >= T.  max_len: rows per sequence, T * page_size when absent.
+    A token with pos[b] < 0, pos[b] + s >= min(cos.shape[0], max_len) or a page id outside 0 .. num_pages - 1 writes nothing to the pools and gets a zero q8 row: the
+    device checks, the host reads neither pos nor the table.  Every written byte equals rope_quantize_qkv_at writing the token into a contiguous cache."""
+    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or tuple(k.shape) != (B, S, Hkv, D):
+        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
+    if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or D % 2 or cos.dim() != 2 or sin.shape != cos.shape or cos.shape[1] != D // 2:
+        raise ValueError(f"cos / sin must be [T, {D // 2}] tables, got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
+    T = cos.shape[0]
+    num_pages, page_size, _, pitch = _kv_pools(k_pool, v_pool, Hkv, D)
+    tw, tp = _block_table(block_table, B)
+    max_len = tw * page_size if max_len is None else int(max_len)
+    if not 0 <= max_len <= tw * page_size:
+        raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence")
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or tuple(pos.shape) != (B,):
+        raise ValueError(f"pos must be an int32 [{B}] tensor, got {getattr(pos, 'dtype', type(pos))} {list(getattr(pos, 'shape', []))}")
+    _hip(q, "q"), _hip(k, "k"), _hip(v, "v"), _hip(k_pool, "k_pool"), _hip(v_pool, "v_pool"), _hip(block_table, "block_table")
+    _operand(cos, "cos", q.dtype, T * (D // 2)), _operand(sin, "sin", q.dtype, T * (D // 2)), _operand(pos, "pos", torch.int32, B)
+    _bump_version(k_pool), _bump_version(v_pool)
+    dev = _same_device(q, k, v, cos, sin, pos, block_table, k_pool, v_pool)
+    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
+    _launch("asq_rope_quantize_qkv_paged", dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[q.dtype], cos.data_ptr(), sin.data_ptr(), T, pos.data_ptr(),
+            block_table.data_ptr(), q8.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), num_pages, page_size, pitch, tp, max_len, float(q_scale), float(k_scale),
+            float(v_scale), B, S, Hq, Hkv, D, _stream(q))
+    return q8, k_pool, v_pool
+
+
+def attn_decode_i8_paged(q, k_pool, v_pool, block_table, kv_len, qk_alpha, pv_alpha, max_len=None):
+    """attn_decode_i8 on paged caches in ONE launch (asq_attn_decode_i8_paged): q int8 [B, Hq, D] or [B, 1, Hq, D], contiguous -> int8 of q's shape.  k_pool / v_pool: int8
+    [num_pages, page_size, Hkv, D] of one shape with strides (pitch, Hkv * D, D, 1) and one pitch, page_size a multiple of 16, read in place.  block_table: int32 [B, T] on
+    the device with row stride >= T; key n of sequence b is row n % page_size of page block_table[b, n // page_size] (ids are clamped to the pool on the device; entries
+    behind a sequence's last page are never read; sequences may share pages).  kv_len, qk_alpha, pv_alpha: attn_decode_i8's; max_len: a bound on the lengths, T * page_size
+    when absent.  Every output byte equals attn_decode_i8 with the same max_len on a contiguous cache that holds each sequence's pages end to end.  Shapes and strides are
+    checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or q.dim() not in (3, 4) or (q.dim() == 4 and q.shape[1] != 1) or not q.is_contiguous():
+        raise ValueError(f"q must be a contiguous int8 [B, Hq, D] or [B, 1, Hq, D] tensor, got {getattr(q, 'dtype', type(q))} {list(getattr(q, 'shape', []))}")
+    B, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
+    num_pages, page_size, Hkv, pitch = _kv_pools(k_pool, v_pool, None, D)
+    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
+        raise ValueError(f"q has {Hq} heads of {D}, the pools {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
+    tw, tp = _block_table(block_table, B)
+    max_len = tw * page_size if max_len is None else int(max_len)
+    if not 0 <= max_len <= tw * page_size or max_len >= 1 << 17 or (max_len > 0 and num_pages == 0):
+        raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence, below 2^17 and 0 for a pool without pages")
+    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
+        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
+    _dev(q, "q"), _hip(k_pool, "k_pool"), _hip(v_pool, "v_pool"), _hip(block_table, "block_table"), _operand(kv_len, "kv_len", torch.int32, B, optional=True)
+    dev = _same_device(q, k_pool, v_pool, block_table, kv_len)
+    out = torch.empty_like(q)
+    _launch("asq_attn_decode_i8_paged", dev, q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), _ptr(kv_len), out.data_ptr(), B, Hq, Hkv, D,
+            num_pages, page_size, pitch, tp, max_len, float(qk_alpha), float(pv_alpha), _stream(q))
+    return out
+
+
 def silu_mul_quantize_fp8(gate, up, fast=None):
     """e4m3(per-token quantise(silu(gate) * up)) in ONE pass (asq_silu_mul_quantize_fp8): (xq float8_e4m3fn [M,K], scale f32 [M,1]) -- what
     quantize_act_fp8(F.silu(gate) * up, "per-token") returns from three.  fast as in silu_mul_quantize (default: the hardware-transcendental SiLU; False: the
