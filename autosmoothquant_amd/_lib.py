@@ -1,4 +1,5 @@
-"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h, include/asq_hip_decode.h and include/asq_hip_paged.h)."""
+"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h, include/asq_hip_decode.h, include/asq_hip_paged.h and
+include/asq_hip_extend.h)."""
 import ctypes
 import os
 import threading
@@ -122,6 +123,13 @@ PAGED_SIGNATURES = {
                                            _i64, _i64, _i64, _i64, _i64, _vp]),
 }
 
+# include/asq_hip_extend.h: several query tokens per sequence under a causal mask on the same caches (speculative verification, chunked prefill, mixed batches), a fifth
+# table: DECODE_SIGNATURES and PAGED_SIGNATURES are tied to their guard-band files; probed by presence, ASQ_VERSION stays
+EXTEND_SIGNATURES = {
+    "asq_attn_extend_i8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
+    "asq_attn_extend_i8_paged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
+}
+
 
 def lib():
     """Load libasq_hip.so once.  Fails loudly: there is no fallback implementation."""
@@ -140,7 +148,8 @@ def lib():
                 # imported torch).  The host side above the C-ABI is torch plumbing anyway (ops.py).
                 import torch  # noqa: F401
                 h = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()) + list(PAGED_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()) + list(PAGED_SIGNATURES.items()) + \
+                        list(EXTEND_SIGNATURES.items()):
                     fn = getattr(h, name)  # AttributeError if the .so lacks a declared symbol
                     fn.restype, fn.argtypes = res, args
                 if h.asq_version() != ASQ_VERSION:   # a stale build: argument lists and the workspace contract may differ

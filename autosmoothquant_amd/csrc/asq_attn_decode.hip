@@ -16,9 +16,12 @@
 //   long    a sequence that fits one chunk computes its scores once.  A longer one walks its chunks twice: pass 1 with sm128's online reference / rescale rule
 //           (the partial sums are rescaled by exp2(o_new - o_old) when a chunk moves the reference), pass 2 recomputes each chunk's scores and does its P . V.
 // No workgroup waits for another, no workspace, no float atomics.  Rows >= n of the cache are never read (load16_guarded / load4_kn against n).
+// The same kernel with the PAGED flag reads pools of pages behind a block table (include/asq_hip_paged.h) and with the MULTI flag attends several query tokens per
+// sequence under a causal mask, T tokens x r heads on the tile's rows (include/asq_hip_extend.h).
 #include "asq_bmm_core.h"
 #include "../../include/asq_hip_decode.h"
 #include "../../include/asq_hip_paged.h"
+#include "../../include/asq_hip_extend.h"
 
 namespace asq {
 
@@ -53,11 +56,32 @@ struct DecPagedArgs : DecArgs {
     int num_pages, page_size;
 };
 
+// asq_attn_extend_i8 / _paged (include/asq_hip_extend.h): Sq query tokens per sequence, right-padded, token s < m_b at key position n_b - m_b + s.  `r` of the base
+// struct is then R = hr * T, the tile rows in use: T tokens of the hr = Hq / Hkv heads of one KV head, row i = token tg * T + i / hr, head g * hr + i % hr
+struct DecMulti {
+    const int32_t *q_len;
+    int Sq, T, hr, groups;   // groups = ceil(Sq / T) token groups per (sequence, KV head)
+};
+struct DecMultiArgs : DecArgs {
+    DecMulti m;
+};
+struct DecMultiPagedArgs : DecPagedArgs {
+    DecMulti m;
+};
+template <bool PAGED, bool MULTI>
+using DecArgsOf = std::conditional_t<MULTI, std::conditional_t<PAGED, DecMultiPagedArgs, DecMultiArgs>, std::conditional_t<PAGED, DecPagedArgs, DecArgs>>;
+
 // ND: 64-byte steps of D (ceil(D / 64)); NW: waves
 // PAGED: the caches are pools of pages behind a block table.  A template flag for GROUPED's reason (asq_bmm.hip): the instantiations without it take DecArgs and
 // compile to what they were.  The one new thing is where a 16-row group of keys starts (page_size % 16 == 0: the 16 keys of a score tile and a lane's 16 V rows lie
 // inside one page); the chunk, the tile -> wave assignment, the strip, the loaders and the merge order are shared, so every output byte is the contiguous form's.
-template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(64 * NW) attn_decode_i8_kernel(const std::conditional_t<PAGED, DecPagedArgs, DecArgs> A)
+// MULTI: several query tokens per sequence under a causal mask, by the same rule: the flagged instantiations take DecMultiArgs / DecMultiPagedArgs, the others compile
+// to what they were.  One workgroup per (sequence, KV head, token group); the tile's rows carry T tokens x hr heads, each row with its own number of keys L_row.  The
+// workgroup's loops run to the largest L of its rows (<= n_b, so the K / V guards and the table rule hold as they are); a row's reference takes the keys < L_row only
+// and the sum and the P formation mask the keys >= L_row with the tail mask's select.  A masked key adds +0.0f to a sum of non-negative terms, a chunk behind L_row
+// leaves the integer reference where it was and rescales by exp2(0), and its P bytes are zero: a row's bytes are those of the unflagged kernel run with n = L_row on
+// the same tile rows (DESIGN.md 4.14's identities).
+template <int ND, int NW, bool PAGED = false, bool MULTI = false> __global__ void __launch_bounds__(64 * NW) attn_decode_i8_kernel(const DecArgsOf<PAGED, MULTI> A)
 {
     extern __shared__ __attribute__((aligned(16))) char dec_lds[];
     constexpr int NT = 64 * NW;
@@ -66,15 +90,60 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
     int *const strip = (int *)dec_lds, *const osum = strip + r * SP, *const wref = osum + r * 64 * ND, *const rowref = wref + NW * 16;
     float *const part = (float *)(rowref + 32);
 
-    const int b = blockIdx.x / A.Hkv, g = blockIdx.x - b * A.Hkv;
+    int b, g;
+    [[maybe_unused]] int tok0 = 0;   // MULTI: the workgroup's first token
+    if constexpr (MULTI) {
+        const int bg = blockIdx.x / A.m.groups;
+        tok0 = (blockIdx.x - bg * A.m.groups) * A.m.T;
+        b = bg / A.Hkv, g = bg - b * A.Hkv;
+    } else {
+        b = blockIdx.x / A.Hkv, g = blockIdx.x - b * A.Hkv;
+    }
     int nb = A.kv_len ? A.kv_len[b] : A.max_len;
     nb = nb < 0 ? 0 : (nb > A.max_len ? A.max_len : nb);
-    const int64_t ld = (int64_t)A.Hkv * D, qoff = ((int64_t)b * A.Hq + (int64_t)g * r) * D;   // the group's r heads are r * D contiguous bytes of q and out
+    // MULTI: token s < mb sees the keys below lbase + s + 1.  row_keys: L of a tile row, 0 for a padded token, a token that sees no key and a row of no token; row_off:
+    // the row's bytes in q and out (a per-row base: the heads of a token are contiguous, the tokens are not), -1 for a token the tensors do not hold.  nb becomes the
+    // workgroup's extent, the largest L of its rows; lrow is the L of the lane's own row t16.
+    [[maybe_unused]] int mb = 0, lbase = 0, lrow = 0;
+    [[maybe_unused]] auto row_keys = [&](int row) -> int {
+        if constexpr (MULTI) {
+            const int64_t tk = (int64_t)tok0 + row / A.m.hr, L = lbase + tk + 1;   // (64-bit: tok0 + 15 may pass 2^31 where Sq nears it)
+            return row < r && tk < mb && L > 0 ? (int)L : 0;
+        } else {
+            return nb;
+        }
+    };
+    [[maybe_unused]] auto row_off = [&](int row) -> int64_t {
+        if constexpr (MULTI) {
+            const int64_t tk = (int64_t)tok0 + row / A.m.hr;
+            const int hd = row - (row / A.m.hr) * A.m.hr;
+            return tk < A.m.Sq ? (((int64_t)b * A.m.Sq + tk) * A.Hq + (int64_t)g * A.m.hr + hd) * D : (int64_t)-1;
+        } else {
+            return 0;
+        }
+    };
+    if constexpr (MULTI) {
+        mb = A.m.q_len ? A.m.q_len[b] : A.m.Sq;
+        mb = mb < 0 ? 0 : (mb > A.m.Sq ? A.m.Sq : mb);
+        lbase = nb - mb;
+        const int tv = mb - tok0 < A.m.T ? mb - tok0 : A.m.T;   // the workgroup's valid tokens: tok0 .. tok0 + tv - 1 (tv <= 0: none); the last sees the most keys
+        nb = tv > 0 && lbase + tok0 + tv > 0 ? lbase + tok0 + tv : 0;
+        lrow = row_keys(t16);
+    }
+    const int64_t ld = (int64_t)A.Hkv * D, qoff = MULTI ? 0 : ((int64_t)b * A.Hq + (int64_t)g * r) * D;   // the group's r heads are r * D contiguous bytes of q and out
     const int64_t seq = PAGED ? 0 : b * A.pitch;   // (PAGED: the page's offset comes per 16-row group, group_at)
     const int8_t *const qb = A.q + qoff, *const kb = A.k + seq + (int64_t)g * D, *const vb = A.v + seq + (int64_t)g * D;
     int8_t *const ob = A.out + qoff;
     if (nb == 0) {   // (the whole workgroup: no barrier has been met)
-        for (int i = tid; i < r * D / 16; i += NT) *(v4i *)(ob + i * 16) = (v4i){0, 0, 0, 0};
+        if constexpr (MULTI) {
+            const int chunks = D / 16;
+            for (int i = tid; i < r * chunks; i += NT) {
+                const int64_t off = row_off(i / chunks);
+                if (off >= 0) *(v4i *)(ob + off + (i % chunks) * 16) = (v4i){0, 0, 0, 0};
+            }
+        } else {
+            for (int i = tid; i < r * D / 16; i += NT) *(v4i *)(ob + i * 16) = (v4i){0, 0, 0, 0};
+        }
         return;
     }
     const bool neg = A.qk_alpha < 0.0f;
@@ -101,12 +170,16 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
 
     v4i fq[ND];   // row t16 of the group's q, 16 bytes at 16 q16 of each 64-byte step
 #pragma unroll
-    for (int ds = 0; ds < ND; ++ds) fq[ds] = load16_guarded(qb, D, t16, r, ds * 64 + q16 * 16, D, true);
+    for (int ds = 0; ds < ND; ++ds) {
+        if constexpr (MULTI) fq[ds] = load16_guarded(qb + (lrow > 0 ? row_off(t16) : 0), D, 0, lrow > 0 ? 1 : 0, ds * 64 + q16 * 16, D, true);   // a row without keys: zeros, nothing read
+        else fq[ds] = load16_guarded(qb, D, t16, r, ds * 64 + q16 * 16, D, true);
+    }
 
     // The scores of keys n0 .. n0 + cn - 1 into the strip; returns the lane's reference over its own (row t16, valid keys).  Tile kt of the chunk belongs to wave kt % NW;
     // a wave has 4 tiles' loads in flight.  A lane's accumulator: row t16, keys 16 kt + 4 q16 .. + 3.
     auto scores = [&](int n0, int cn) -> int {
         const int tiles = (cn + 15) >> 4;
+        const int rl = MULTI ? (lrow - n0 < cn ? lrow - n0 : cn) : cn;   // MULTI: the keys of the chunk that row t16 sees
         int tm = ref0;
         for (int kt0 = wave; kt0 < tiles; kt0 += 4 * NW) {
             v4i fk[4][ND];
@@ -139,7 +212,7 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
                         *(v4i *)(strip + t16 * SP + key) = acc;
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            if (key + e < cn) tm = better(tm, acc[e]);
+                            if (key + e < rl) tm = better(tm, acc[e]);
                     }
                 }
             }
@@ -166,13 +239,14 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
         __syncthreads();
         for (int row = 0; row < r; ++row) {   // every wave: its key slices of every row
             const float on = -(float)rowref[(par ^ 1) * 16 + row] * c, oo = -(float)rowref[par * 16 + row] * c;
+            const int rl = MULTI ? (row_keys(row) - n0 < cn ? row_keys(row) - n0 : cn) : cn;
             float sum = 0.0f;
             for (int n = (wave * 64 + lane) * 4; n < cn; n += NT * 4) {
                 const v4i s = *(const v4i *)(strip + row * SP + n);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float ex = __builtin_amdgcn_exp2f(__builtin_fmaf((float)s[e], c, on));
-                    sum += n + e < cn ? ex : 0.0f;
+                    sum += n + e < rl ? ex : 0.0f;
                 }
             }
 #pragma unroll
@@ -206,6 +280,7 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
             scores(n0, cn);
             __syncthreads();
         }
+        const int rl = MULTI ? (lrow - n0 < cn ? lrow - n0 : cn) : cn;
         for (int ks = wave; ks * 64 < cn; ks += NW) {
             const int key = ks * 64 + q16 * 16;   // the lane's 16 keys, chunk-relative
             uint32_t rows[ND][16];
@@ -219,7 +294,7 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
                     else rows[cb][i] = load4_kn(vb, ld, D, n0 + key + i, n0 + cn, cb * 64 + 4 * t16, true);
                 }
             v4i fp = (v4i){0, 0, 0, 0};
-            if (t16 < r && key < cn) {
+            if (t16 < r && key < rl) {
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
                     const v4i s = *(const v4i *)(strip + t16 * SP + key + 4 * w);
@@ -227,7 +302,7 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float ex = __builtin_amdgcn_exp2f(__builtin_fmaf((float)s[e], c, o));
-                        ex = key + 4 * w + e < cn ? ex : 0.0f;
+                        ex = key + 4 * w + e < rl ? ex : 0.0f;
                         p[e] = __float_as_uint(__builtin_fmaf(ex, inv, SM_MAGIC));   // low byte: rne(127 p), 0 .. 127
                     }
                     fp[w] = (int)(__builtin_amdgcn_perm(p[1], p[0], 0x0c0c0400u) | __builtin_amdgcn_perm(p[3], p[2], 0x04000c0cu));
@@ -265,6 +340,14 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
     for (int i = tid; i < r * chunks; i += NT) {
         const int row = i / chunks, ch = i - row * chunks;
         const int *const s = osum + row * 64 * ND + ch * 16;
+        if constexpr (MULTI) {   // a row without keys is zeros whatever its sums hold; a row of no token is not written
+            const int64_t off = row_off(row);
+            if (off < 0) continue;
+            if (row_keys(row) == 0) {
+                *(v4i *)(ob + off + ch * 16) = (v4i){0, 0, 0, 0};
+                continue;
+            }
+        }
         v4i v;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
@@ -272,7 +355,8 @@ template <int ND, int NW, bool PAGED = false> __global__ void __launch_bounds__(
             v[w] = (int)(((uint32_t)epi.one(a[0], 0) & 0xFF) | (((uint32_t)epi.one(a[1], 0) & 0xFF) << 8) | (((uint32_t)epi.one(a[2], 0) & 0xFF) << 16) |
                          (((uint32_t)epi.one(a[3], 0) & 0xFF) << 24));
         }
-        *(v4i *)(ob + row * D + ch * 16) = v;
+        if constexpr (MULTI) *(v4i *)(ob + row_off(row) + ch * 16) = v;
+        else *(v4i *)(ob + row * D + ch * 16) = v;
     }
 }
 
@@ -286,15 +370,22 @@ static int dec_waves()
     return nw;
 }
 
-template <int ND, bool PAGED = false> static int launch_decode(const std::conditional_t<PAGED, DecPagedArgs, DecArgs> &a, int64_t grid, hipStream_t s)
+template <int ND, bool PAGED = false, bool MULTI = false> static int launch_decode(const DecArgsOf<PAGED, MULTI> &a, int64_t grid, hipStream_t s)
 {
     const int nw = ND > 2 && dec_waves() == 16 ? 8 : dec_waves();   // D > 128 at 16 waves (128 VGPRs) would spill: not instantiated
     const size_t lds = (size_t)dec_lds_bytes(a.r, a.chunk, ND, nw);
-    const char *const what = PAGED ? "asq_attn_decode_i8_paged" : "asq_attn_decode_i8";
-    if (nw == 4) return launch_lds(what, attn_decode_i8_kernel<ND, 4, PAGED>, DEC_LDS_MAX, lds, grid, 256, s, a);
+    const char *const what = MULTI ? (PAGED ? "asq_attn_extend_i8_paged" : "asq_attn_extend_i8") : (PAGED ? "asq_attn_decode_i8_paged" : "asq_attn_decode_i8");
+    if (nw == 4) return launch_lds(what, attn_decode_i8_kernel<ND, 4, PAGED, MULTI>, DEC_LDS_MAX, lds, grid, 256, s, a);
     if constexpr (ND <= 2)
-        if (nw == 16) return launch_lds(what, attn_decode_i8_kernel<ND, 16, PAGED>, DEC_LDS_MAX, lds, grid, 1024, s, a);
-    return launch_lds(what, attn_decode_i8_kernel<ND, 8, PAGED>, DEC_LDS_MAX, lds, grid, 512, s, a);
+        if (nw == 16) return launch_lds(what, attn_decode_i8_kernel<ND, 16, PAGED, MULTI>, DEC_LDS_MAX, lds, grid, 1024, s, a);
+    return launch_lds(what, attn_decode_i8_kernel<ND, 8, PAGED, MULTI>, DEC_LDS_MAX, lds, grid, 512, s, a);
+}
+
+// the token split of asq_attn_extend_i8 / _paged: T = min(Sq, 16 / hr) tokens per workgroup, R = hr * T tile rows, ceil(Sq / T) token groups per (sequence, KV head)
+static DecMulti dec_multi(const int32_t *q_len, int64_t Sq, int hr)
+{
+    const int T = (int)(Sq < 16 / hr ? Sq : 16 / hr);
+    return DecMulti{q_len, (int)Sq, T, hr, (int)((Sq + T - 1) / T)};
 }
 
 }  // namespace asq
@@ -370,4 +461,88 @@ extern "C" int asq_attn_decode_i8_paged(const int8_t *q, const int8_t *k_pool, c
     default: rc = launch_decode<4, true>(a, grid, st); break;
     }
     return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_decode_i8_paged");
+}
+
+// ---- include/asq_hip_extend.h: Sq query tokens per sequence under a causal mask (the MULTI forms) ----------------------------------------------------------------
+extern "C" int asq_attn_extend_i8(const int8_t *q, const int8_t *k_cache, const int8_t *v_cache, const int32_t *kv_len, const int32_t *q_len, int8_t *out, int64_t B,
+                                  int64_t Sq, int64_t Hq, int64_t Hkv, int64_t D, int64_t kv_batch_pitch, int64_t max_len, float qk_alpha, float pv_alpha, void *stream)
+{
+    const AsqRange range_("asq_attn_extend_i8");
+    const int64_t lim = 1ll << 31;
+    ASQ_REQUIRE(B >= 0 && Sq >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Sq < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17),
+                ASQ_ERR_DIM, "asq_attn_extend_i8: bad dims B=%lld Sq=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld", (long long)B, (long long)Sq, (long long)Hq, (long long)Hkv,
+                (long long)D, (long long)max_len);
+    int64_t bh = 0, grid = 0, qn = 0;   // B * Hkv (sequence, KV head) pairs; B * Sq * Hq * D bytes of q and out
+    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &bh) && bh < lim && !__builtin_mul_overflow(B * Sq, Hq, &qn) && !__builtin_mul_overflow(qn, D, &qn), ASQ_ERR_DIM,
+                "asq_attn_extend_i8: dims overflow");
+    if (B == 0 || Sq == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(q && k_cache && v_cache && out, ASQ_ERR_NULL, "asq_attn_extend_i8: NULL pointer");
+    const int64_t cache = max_len * Hkv * D, kvb = kv_batch_pitch == 0 ? cache : kv_batch_pitch;   // (< 2^17 * 2^31 * 2^8)
+    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM, "asq_attn_extend_i8: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)",
+                (long long)Hq, (long long)Hkv, (long long)D);
+    const DecMulti m = dec_multi(q_len, Sq, (int)(Hq / Hkv));
+    ASQ_REQUIRE(!__builtin_mul_overflow(bh, (int64_t)m.groups, &grid) && grid < lim, ASQ_ERR_DIM, "asq_attn_extend_i8: %lld x %lld x %d workgroups do not fit a 31-bit grid",
+                (long long)B, (long long)Hkv, m.groups);
+    ASQ_REQUIRE(kvb >= cache && kvb % 16 == 0 && kvb <= (1ll << 60) / B, ASQ_ERR_DIM, "asq_attn_extend_i8: kv_batch_pitch must be 0 (dense) or >= max_len * Hkv * D and a multiple of 16");
+    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_cache) | ((uintptr_t)v_cache) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN, "asq_attn_extend_i8: q, the caches and out must be 16-B aligned");
+    ASQ_REQUIRE((((uintptr_t)kv_len | (uintptr_t)q_len) & 3) == 0, ASQ_ERR_ALIGN, "asq_attn_extend_i8: kv_len and q_len must be 4-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int R = m.hr * m.T;
+    const DecMultiArgs a{{q, k_cache, v_cache, kv_len, out, kvb, (int)Hq, (int)Hkv, (int)D, R, (int)max_len, dec_chunk(R, max_len), qk_alpha, pv_alpha}, m};
+    int rc;
+    switch ((D + 63) / 64) {
+    case 1: rc = launch_decode<1, false, true>(a, grid, st); break;
+    case 2: rc = launch_decode<2, false, true>(a, grid, st); break;
+    case 3: rc = launch_decode<3, false, true>(a, grid, st); break;
+    default: rc = launch_decode<4, false, true>(a, grid, st); break;
+    }
+    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_extend_i8");
+}
+
+extern "C" int asq_attn_extend_i8_paged(const int8_t *q, const int8_t *k_pool, const int8_t *v_pool, const int32_t *block_table, const int32_t *kv_len, const int32_t *q_len,
+                                        int8_t *out, int64_t B, int64_t Sq, int64_t Hq, int64_t Hkv, int64_t D, int64_t num_pages, int64_t page_size, int64_t page_pitch,
+                                        int64_t table_pitch, int64_t max_len, float qk_alpha, float pv_alpha, void *stream)
+{
+    const AsqRange range_("asq_attn_extend_i8_paged");
+    const int64_t lim = 1ll << 31;
+    ASQ_REQUIRE(B >= 0 && Sq >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Sq < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17) &&
+                    num_pages >= 0 && num_pages < lim && page_size >= 0 && page_size < lim && table_pitch >= 0 && table_pitch < lim,
+                ASQ_ERR_DIM, "asq_attn_extend_i8_paged: bad dims B=%lld Sq=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld num_pages=%lld page_size=%lld table_pitch=%lld", (long long)B,
+                (long long)Sq, (long long)Hq, (long long)Hkv, (long long)D, (long long)max_len, (long long)num_pages, (long long)page_size, (long long)table_pitch);
+    int64_t bh = 0, grid = 0, qn = 0, page = 0;   // as asq_attn_extend_i8; a page holds page_size * Hkv * D bytes
+    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &bh) && bh < lim && !__builtin_mul_overflow(B * Sq, Hq, &qn) && !__builtin_mul_overflow(qn, D, &qn) &&
+                    !__builtin_mul_overflow(page_size * Hkv, D, &page) && page <= (1ll << 60),
+                ASQ_ERR_DIM, "asq_attn_extend_i8_paged: dims overflow");
+    if (B == 0 || Sq == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(q && k_pool && v_pool && block_table && out, ASQ_ERR_NULL, "asq_attn_extend_i8_paged: NULL pointer");
+    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM,
+                "asq_attn_extend_i8_paged: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)", (long long)Hq, (long long)Hkv, (long long)D);
+    const DecMulti m = dec_multi(q_len, Sq, (int)(Hq / Hkv));
+    ASQ_REQUIRE(!__builtin_mul_overflow(bh, (int64_t)m.groups, &grid) && grid < lim, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: %lld x %lld x %d workgroups do not fit a 31-bit grid",
+                (long long)B, (long long)Hkv, m.groups);
+    const int64_t pp = page_pitch == 0 ? page : page_pitch;
+    ASQ_REQUIRE(page_size > 0 && page_size % 16 == 0, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: page_size must be a positive multiple of 16, got %lld", (long long)page_size);
+    ASQ_REQUIRE(pp >= page && pp % 16 == 0 && pp <= (1ll << 60) / (num_pages > 0 ? num_pages : 1), ASQ_ERR_DIM,
+                "asq_attn_extend_i8_paged: page_pitch must be 0 (dense) or >= page_size * Hkv * D and a multiple of 16");
+    ASQ_REQUIRE(max_len <= table_pitch * page_size, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: max_len %lld needs more than the %lld table entries of %lld keys a sequence has",
+                (long long)max_len, (long long)table_pitch, (long long)page_size);
+    ASQ_REQUIRE(max_len == 0 || num_pages > 0, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: max_len %lld with a pool of no pages", (long long)max_len);
+    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_pool) | ((uintptr_t)v_pool) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN,
+                "asq_attn_extend_i8_paged: q, the pools and out must be 16-B aligned");
+    ASQ_REQUIRE((((uintptr_t)kv_len | (uintptr_t)q_len | (uintptr_t)block_table) & 3) == 0, ASQ_ERR_ALIGN,
+                "asq_attn_extend_i8_paged: kv_len, q_len and block_table must be 4-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int R = m.hr * m.T;
+    DecMultiPagedArgs a{};
+    static_cast<DecPagedArgs &>(a) = DecPagedArgs{{q, k_pool, v_pool, kv_len, out, pp, (int)Hq, (int)Hkv, (int)D, R, (int)max_len, dec_chunk(R, max_len), qk_alpha, pv_alpha},
+                                                  block_table, table_pitch, (int)num_pages, (int)page_size};
+    a.m = m;
+    int rc;
+    switch ((D + 63) / 64) {
+    case 1: rc = launch_decode<1, true, true>(a, grid, st); break;
+    case 2: rc = launch_decode<2, true, true>(a, grid, st); break;
+    case 3: rc = launch_decode<3, true, true>(a, grid, st); break;
+    default: rc = launch_decode<4, true, true>(a, grid, st); break;
+    }
+    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_extend_i8_paged");
 }

@@ -18,7 +18,10 @@ A batch of sequences of different lengths takes a decode step in two launches: R
 position (ops.rope_quantize_qkv_at), Int8Attention.decode attends over each sequence's own number of keys on the cache where it lies (ops.attn_decode_i8).
 
 The same step on a paged cache -- fixed-size pages handed out from one pool, a block table per sequence, what a vLLM-style server keeps -- is RopeQuantQKV with a
-PagedInt8KVCache (ops.rope_quantize_qkv_paged) and Int8Attention.decode_paged (ops.attn_decode_i8_paged): the same two launches, the same bytes."""
+PagedInt8KVCache (ops.rope_quantize_qkv_paged) and Int8Attention.decode_paged (ops.attn_decode_i8_paged): the same two launches, the same bytes.
+
+A step that carries several tokens per sequence -- draft tokens to verify, a prompt chunk, a mixed batch -- is the same append followed by Int8Attention.extend /
+extend_paged (ops.attn_extend_i8 / _paged): every token under a causal mask over its sequence's keys up to its own, one launch; cache.rewind drops what was rejected."""
 import torch
 
 from ... import ops
@@ -125,6 +128,23 @@ class Int8Attention(torch.nn.Module):
             raise ValueError(f"q8 must be [B, 1, Hq, d], got {list(getattr(q8, 'shape', []))}")
         return ops.attn_decode_i8_paged(q8, k_pool, v_pool, block_table, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), max_len=max_len)
 
+    def extend(self, q8, k_cache, v_cache, kv_len=None, q_len=None, max_len=None):
+        """A step of several tokens per sequence under a causal mask in ONE launch (ops.attn_extend_i8): q8 int8 [B, Sq, Hq, d] -> [B, Sq, Hq, d], the append's q8 over the
+        caches the append has just written (kv_len includes the new tokens).  Sequence b brings q_len[b] tokens (int32 [B] on the device, right-padded; None: Sq each);
+        token s sits at key position kv_len[b] - q_len[b] + s and sees the keys up to and including its own; padded tokens get zero rows.  The verification of draft
+        tokens (followed by cache.rewind of the rejected ones), a prompt chunk, a mixed batch.  With Sq * r <= 16 the step costs about one decode launch; a long prefill
+        stays with forward(layout="bshd")."""
+        if not torch.is_tensor(q8) or q8.dim() != 4:
+            raise ValueError(f"q8 must be [B, Sq, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        return ops.attn_extend_i8(q8, k_cache, v_cache, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), q_len=q_len, max_len=max_len)
+
+    def extend_paged(self, q8, k_pool, v_pool, block_table, kv_len=None, q_len=None, max_len=None):
+        """extend on a paged cache, ONE launch (ops.attn_extend_i8_paged): the pools and the table as in decode_paged, q8, q_len and the per-token rule as in extend.  The
+        output bytes are extend's on a contiguous cache holding the same keys."""
+        if not torch.is_tensor(q8) or q8.dim() != 4:
+            raise ValueError(f"q8 must be [B, Sq, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        return ops.attn_extend_i8_paged(q8, k_pool, v_pool, block_table, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), q_len=q_len, max_len=max_len)
+
 
 class Int8KVCache:
     """A preallocated int8 KV cache in the token-major layout: k and v [B, Smax, Hkv, d] and the number of tokens held, `length` (one position for the whole batch).
@@ -161,8 +181,9 @@ class RaggedInt8KVCache:
     """Int8KVCache with a length per sequence: k and v [B, Smax, Hkv, d], `kv_len` int32 [B] on the cache's device -- what the kernels read: the append position of
     ops.rope_quantize_qkv_at, the number of keys of ops.attn_decode_i8, so a captured step replays as the lengths move -- and its host mirror `lengths`, a list of
     ints, which serves the bounds checks (ValueError, no device sync).
-    advance(S): S an int (every sequence) or B ints -> lengths += S, one stream-ordered add_ on kv_len.  reset(b=None): every sequence, or sequence b, back to 0
-    (it forgets, it does not clear).  bound() = max(lengths): a tighter max_len for attn_decode_i8 than the capacity."""
+    advance(S): S an int (every sequence) or B ints -> lengths += S, one stream-ordered add_ on kv_len.  rewind(S): lengths -= S, one stream-ordered sub_ (the rejected
+    tokens of a speculative step; ValueError, nothing changed, for a negative step or one beyond a length).  reset(b=None): every sequence, or sequence b, back to 0.
+    rewind and reset forget, they do not clear.  bound() = max(lengths): a tighter max_len for attn_decode_i8 than the capacity."""
 
     def __init__(self, batch, max_len, kv_heads, head_dim, device=None):
         self.k = torch.zeros((batch, max_len, kv_heads, head_dim), dtype=torch.int8, device=device)
@@ -188,6 +209,16 @@ class RaggedInt8KVCache:
             self.kv_len.add_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
         self.lengths = [n + s for n, s in zip(self.lengths, steps)]
 
+    def rewind(self, S):
+        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
+        if len(steps) != len(self.lengths) or any(s < 0 or s > n for s, n in zip(steps, self.lengths)):
+            raise ValueError(f"RaggedInt8KVCache: {steps} tokens cannot be taken back from {len(self.lengths)} sequences of lengths {self.lengths}")
+        if isinstance(S, int):
+            self.kv_len.sub_(S)
+        else:
+            self.kv_len.sub_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
+        self.lengths = [n - s for n, s in zip(self.lengths, steps)]
+
     def reset(self, b=None):
         if b is None:
             self.kv_len.zero_()
@@ -208,10 +239,11 @@ class PagedInt8KVCache:
     (pages are handed out in ascending order at first, a freed page is the next one reused).  Memory follows the real lengths: a sequence holds ceil(n / page_size)
     pages once reserve() has covered its n tokens.
     reserve(S): the pages the next S tokens (an int, or one per sequence) need, taken from the free list and written into the table; ValueError before anything is
-    touched when the pool or max_len does not suffice.  advance(S): lengths += S within what is reserved.  reset(b=None): every sequence, or sequence b, back to 0,
-    its pages back to the free list (it forgets, it does not clear; stale table entries stay behind the length, where no kernel reads them).  bound() = max(lengths).
-    gather(b) -> sequence b's keys and values as contiguous [n_b, Hkv, d] tensors by plain torch indexing: for tests, and for a chunked prefill through
-    Int8Attention.forward(layout="bshd").  A refused call changes no state."""
+    touched when the pool or max_len does not suffice.  advance(S): lengths += S within what is reserved.  rewind(S): lengths -= S (the rejected tokens of a speculative
+    step), the pages wholly behind ceil(length / page_size) back to the free list, newest first.  reset(b=None): every sequence, or sequence b, back to 0, its pages
+    back to the free list.  rewind and reset forget, they do not clear; stale table entries stay behind the length, where no kernel reads them.  bound() = max(lengths).
+    gather(b) -> sequence b's keys and values as contiguous [n_b, Hkv, d] tensors by plain torch indexing: for tests and for callers that want a sequence as one
+    tensor (a step of several tokens runs on the pool in place: Int8Attention.extend_paged).  A refused call changes no state."""
 
     def __init__(self, num_pages, page_size, kv_heads, head_dim, batch, max_len, device=None):
         if num_pages < 0 or page_size <= 0 or page_size % 16 or batch < 0 or max_len < 0:
@@ -266,6 +298,17 @@ class PagedInt8KVCache:
         else:
             self.kv_len.add_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
         self.lengths = [n + s for n, s in zip(self.lengths, steps)]
+
+    def rewind(self, S):
+        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
+        if len(steps) != len(self.lengths) or any(s < 0 or s > n for s, n in zip(steps, self.lengths)):
+            raise ValueError(f"PagedInt8KVCache.rewind: {steps} tokens cannot be taken back from {len(self.lengths)} sequences of lengths {self.lengths}")
+        if isinstance(S, int):
+            self.kv_len.sub_(S)
+        else:
+            self.kv_len.sub_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
+        self.lengths = [n - s for n, s in zip(self.lengths, steps)]
+        self._unreserve([-(-n // self.page_size) for n in self.lengths])
 
     def reset(self, b=None):
         if b is None:

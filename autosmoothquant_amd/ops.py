@@ -922,6 +922,63 @@ def attn_decode_i8_paged(q, k_pool, v_pool, block_table, kv_len, qk_alpha, pv_al
     return out
 
 
+def _extend_q(q, q_len):
+    """q and q_len of the extend ops: a contiguous int8 [B, Sq, Hq, D] tensor, q_len None or int32 [B] -> (B, Sq, Hq, D)"""
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or q.dim() != 4 or not q.is_contiguous():
+        raise ValueError(f"q must be a contiguous int8 [B, Sq, Hq, D] tensor, got {getattr(q, 'dtype', type(q))} {list(getattr(q, 'shape', []))}")
+    if q_len is not None and (not isinstance(q_len, torch.Tensor) or q_len.dtype != torch.int32 or tuple(q_len.shape) != (q.shape[0],)):
+        raise ValueError(f"q_len must be None or an int32 [{q.shape[0]}] tensor, got {getattr(q_len, 'dtype', type(q_len))} {list(getattr(q_len, 'shape', []))}")
+    return tuple(q.shape)
+
+
+def attn_extend_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, q_len=None, max_len=None):
+    """Causal int8 attention of Sq query tokens per sequence for a ragged batch in ONE launch (asq_attn_extend_i8): q int8 [B, Sq, Hq, D], contiguous (the append's q8) ->
+    int8 of q's shape.  k_cache, v_cache, kv_len, qk_alpha, pv_alpha, max_len: attn_decode_i8's; kv_len[b] includes the step's new tokens (the append runs first).
+    q_len: int32 [B] on the device, the tokens of sequence b that count (clamped to 0 .. Sq; None: Sq each); the tokens are right-padded, token s < q_len[b] is the query
+    at key position kv_len[b] - q_len[b] + s and sees the keys up to and including its own.  A padded token, and one that would see no key, gets a zero row.  Token (b, s)
+    is attn_decode_i8's arithmetic over its own keys; min(Sq, 16 // r) tokens share a workgroup and one read of K and V.  Shapes and strides are checked first (ValueError),
+    then the devices (RuntimeError: no CPU fallback)."""
+    B, Sq, Hq, D = _extend_q(q, q_len)
+    smax, Hkv, kvb = _kv_caches(k_cache, v_cache, B, None, D)
+    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
+        raise ValueError(f"q has {Hq} heads of {D}, the caches {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
+    max_len = smax if max_len is None else int(max_len)
+    if not 0 <= max_len <= smax or max_len >= 1 << 17:
+        raise ValueError(f"max_len {max_len} must be within the caches' {smax} rows and below 2^17")
+    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
+        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
+    _dev(q, "q"), _hip(k_cache, "k_cache"), _hip(v_cache, "v_cache")
+    _operand(kv_len, "kv_len", torch.int32, B, optional=True), _operand(q_len, "q_len", torch.int32, B, optional=True)
+    dev = _same_device(q, k_cache, v_cache, kv_len, q_len)
+    out = torch.empty_like(q)
+    _launch("asq_attn_extend_i8", dev, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(kv_len), _ptr(q_len), out.data_ptr(), B, Sq, Hq, Hkv, D, kvb, max_len,
+            float(qk_alpha), float(pv_alpha), _stream(q))
+    return out
+
+
+def attn_extend_i8_paged(q, k_pool, v_pool, block_table, kv_len, qk_alpha, pv_alpha, q_len=None, max_len=None):
+    """attn_extend_i8 on paged caches in ONE launch (asq_attn_extend_i8_paged): q int8 [B, Sq, Hq, D], contiguous -> int8 of q's shape.  k_pool, v_pool, block_table,
+    kv_len, max_len: attn_decode_i8_paged's; q_len and the per-token rule: attn_extend_i8's.  Every output byte equals attn_extend_i8 with the same max_len on a contiguous
+    cache that holds each sequence's pages end to end.  Shapes and strides are checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
+    B, Sq, Hq, D = _extend_q(q, q_len)
+    num_pages, page_size, Hkv, pitch = _kv_pools(k_pool, v_pool, None, D)
+    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
+        raise ValueError(f"q has {Hq} heads of {D}, the pools {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
+    tw, tp = _block_table(block_table, B)
+    max_len = tw * page_size if max_len is None else int(max_len)
+    if not 0 <= max_len <= tw * page_size or max_len >= 1 << 17 or (max_len > 0 and num_pages == 0):
+        raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence, below 2^17 and 0 for a pool without pages")
+    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
+        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
+    _dev(q, "q"), _hip(k_pool, "k_pool"), _hip(v_pool, "v_pool"), _hip(block_table, "block_table")
+    _operand(kv_len, "kv_len", torch.int32, B, optional=True), _operand(q_len, "q_len", torch.int32, B, optional=True)
+    dev = _same_device(q, k_pool, v_pool, block_table, kv_len, q_len)
+    out = torch.empty_like(q)
+    _launch("asq_attn_extend_i8_paged", dev, q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), _ptr(kv_len), _ptr(q_len), out.data_ptr(), B, Sq,
+            Hq, Hkv, D, num_pages, page_size, pitch, tp, max_len, float(qk_alpha), float(pv_alpha), _stream(q))
+    return out
+
+
 def silu_mul_quantize_fp8(gate, up, fast=None):
     """e4m3(per-token quantise(silu(gate) * up)) in ONE pass (asq_silu_mul_quantize_fp8): (xq float8_e4m3fn [M,K], scale f32 [M,1]) -- what
     quantize_act_fp8(F.silu(gate) * up, "per-token") returns from three.  fast as in silu_mul_quantize (default: the hardware-transcendental SiLU; False: the
