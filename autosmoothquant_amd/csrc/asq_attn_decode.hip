@@ -19,6 +19,7 @@
 // The same kernel with the PAGED flag reads pools of pages behind a block table (include/asq_hip_paged.h) and with the MULTI flag attends several query tokens per
 // sequence under a causal mask, T tokens x r heads on the tile's rows (include/asq_hip_extend.h).
 #include "asq_bmm_core.h"
+#include "asq_paged.h"
 #include "../../include/asq_hip_decode.h"
 #include "../../include/asq_hip_paged.h"
 #include "../../include/asq_hip_extend.h"
@@ -388,161 +389,124 @@ static DecMulti dec_multi(const int32_t *q_len, int64_t Sq, int hr)
     return DecMulti{q_len, (int)Sq, T, hr, (int)((Sq + T - 1) / T)};
 }
 
+// ---- the host side, once for the four entries ("how an entry of this family is put together") ---------------------------------------------------
+// What an entry was called with.  The two form bits pick the kernel flags; a decode entry is the multi form's Sq = 1 without q_len, a contiguous entry leaves table and
+// pg alone.  A new rule goes into attn_i8 below, a new form is a bit here and a branch in dec_args.
+struct DecCall {
+    const char *what;   // the entry's name, in every error text
+    bool paged, multi;
+    const int8_t *q, *k, *v;   // k / v: the caches, or the pools
+    const int32_t *table, *kv_len, *q_len;
+    int8_t *out;
+    int64_t B, Sq, Hq, Hkv, D, max_len;
+    int64_t pitch;   // !paged: kv_batch_pitch as given (0: dense)
+    AsqPaged pg;     // paged: num_pages, page_size, page_pitch, table_pitch as given
+    float qk_alpha, pv_alpha;
+};
+
+// the kernel arguments of a form from the common part, the call and the token split
+template <bool PAGED, bool MULTI> static DecArgsOf<PAGED, MULTI> dec_args(const DecArgs &base, const DecCall &c, const DecMulti &m)
+{
+    if constexpr (PAGED) {
+        const DecPagedArgs p{base, c.table, c.pg.table_pitch, (int)c.pg.num_pages, (int)c.pg.page_size};
+        if constexpr (MULTI) return DecMultiPagedArgs{p, m};
+        else return p;
+    } else {
+        if constexpr (MULTI) return DecMultiArgs{base, m};
+        else return base;
+    }
+}
+
+// ceil(D / 64) as a compile-time constant: returns f(std::integral_constant<int, ND>{}) (asq_dispatch_dt's way)
+template <class F> static int dec_dispatch_nd(int64_t D, F &&f)
+{
+    switch ((D + 63) / 64) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
+// The rules of a call in the order the headers state -- dims and overflow, nothing to do, NULL, the shape rules, 16-B then 4-B alignment -- then the grid, the kernel
+// arguments and the launch.
+static int attn_i8(DecCall c, void *stream)
+{
+    const AsqRange range_(c.what);
+    const int64_t lim = 1ll << 31;
+    ASQ_REQUIRE(c.B >= 0 && c.Sq >= 0 && c.Hq >= 0 && c.Hkv >= 0 && c.B < lim && c.Sq < lim && c.Hq < lim && c.Hkv < lim && c.D > 0 && c.D <= 256 && c.max_len >= 0 &&
+                    c.max_len < (1ll << 17),
+                ASQ_ERR_DIM, "%s: bad dims B=%lld Sq=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld", c.what, (long long)c.B, (long long)c.Sq, (long long)c.Hq, (long long)c.Hkv,
+                (long long)c.D, (long long)c.max_len);
+    int64_t bh = 0, grid = 0, qn = 0;   // B * Hkv (sequence, KV head) pairs; B * Sq * Hq * D bytes of q and out
+    ASQ_REQUIRE(!__builtin_mul_overflow(c.B, c.Hkv, &bh) && bh < lim && !__builtin_mul_overflow(c.B * c.Sq, c.Hq, &qn) && !__builtin_mul_overflow(qn, c.D, &qn), ASQ_ERR_DIM,
+                "%s: dims overflow", c.what);
+    if (c.paged)
+        if (const int rc = c.pg.dims(c.what, c.Hkv, c.D)) return rc;
+    if (c.B == 0 || c.Sq == 0 || c.Hq == 0 || c.Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(c.q && c.k && c.v && c.out && (c.table || !c.paged), ASQ_ERR_NULL, "%s: NULL pointer", c.what);
+    ASQ_REQUIRE(c.D % 16 == 0 && c.Hq % c.Hkv == 0 && c.Hq / c.Hkv <= 16, ASQ_ERR_DIM, "%s: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)",
+                c.what, (long long)c.Hq, (long long)c.Hkv, (long long)c.D);
+    const DecMulti m = dec_multi(c.q_len, c.Sq, (int)(c.Hq / c.Hkv));   // (a decode entry: one token, one group)
+    ASQ_REQUIRE(!__builtin_mul_overflow(bh, (int64_t)m.groups, &grid) && grid < lim, ASQ_ERR_DIM, "%s: %lld x %lld x %d workgroups do not fit a 31-bit grid", c.what,
+                (long long)c.B, (long long)c.Hkv, m.groups);
+    int64_t pitch;   // bytes between sequences of the caches, or between pages of the pools
+    if (c.paged) {
+        if (const int rc = c.pg.shape(c.what, c.max_len)) return rc;
+        pitch = c.pg.pitch();
+    } else {
+        const int64_t cache = c.max_len * c.Hkv * c.D;   // (< 2^17 * 2^31 * 2^8)
+        pitch = c.pitch == 0 ? cache : c.pitch;
+        ASQ_REQUIRE(pitch >= cache && pitch % 16 == 0 && pitch <= (1ll << 60) / c.B, ASQ_ERR_DIM, "%s: kv_batch_pitch must be 0 (dense) or >= max_len * Hkv * D and a multiple of 16",
+                    c.what);
+    }
+    ASQ_REQUIRE(((((uintptr_t)c.q) | ((uintptr_t)c.k) | ((uintptr_t)c.v) | ((uintptr_t)c.out)) & 15) == 0, ASQ_ERR_ALIGN, "%s: q, the %s and out must be 16-B aligned", c.what,
+                c.paged ? "pools" : "caches");
+    ASQ_REQUIRE((((uintptr_t)c.kv_len | (uintptr_t)c.q_len | (uintptr_t)c.table) & 3) == 0, ASQ_ERR_ALIGN, "%s: %s must be 4-B aligned", c.what,
+                c.multi ? (c.paged ? "kv_len, q_len and block_table" : "kv_len and q_len") : (c.paged ? "kv_len and block_table" : "kv_len"));
+    hipStream_t st = (hipStream_t)stream;
+    const int R = m.hr * m.T;   // the tile rows in use
+    const DecArgs base{c.q, c.k, c.v, c.kv_len, c.out, pitch, (int)c.Hq, (int)c.Hkv, (int)c.D, R, (int)c.max_len, dec_chunk(R, c.max_len), c.qk_alpha, c.pv_alpha};
+    const int rc = asq_dispatch_bool(c.paged, [&](auto paged) {
+        return asq_dispatch_bool(c.multi, [&](auto multi) {
+            return dec_dispatch_nd(c.D, [&](auto nd) {
+                return launch_decode<decltype(nd)::value, decltype(paged)::value, decltype(multi)::value>(dec_args<decltype(paged)::value, decltype(multi)::value>(base, c, m), grid, st);
+            });
+        });
+    });
+    return rc != ASQ_OK ? rc : asq_after_launch(st, c.what);
+}
+
 }  // namespace asq
 using namespace asq;
 
 extern "C" int asq_attn_decode_i8(const int8_t *q, const int8_t *k_cache, const int8_t *v_cache, const int32_t *kv_len, int8_t *out, int64_t B, int64_t Hq, int64_t Hkv,
                                   int64_t D, int64_t kv_batch_pitch, int64_t max_len, float qk_alpha, float pv_alpha, void *stream)
 {
-    const AsqRange range_("asq_attn_decode_i8");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17), ASQ_ERR_DIM,
-                "asq_attn_decode_i8: bad dims B=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld", (long long)B, (long long)Hq, (long long)Hkv, (long long)D, (long long)max_len);
-    int64_t grid = 0, qn = 0;   // B * Hkv workgroups on a 31-bit grid; B * Hq * D bytes of q and out
-    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &grid) && grid < lim && !__builtin_mul_overflow(B * Hq, D, &qn), ASQ_ERR_DIM, "asq_attn_decode_i8: dims overflow");
-    if (B == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k_cache && v_cache && out, ASQ_ERR_NULL, "asq_attn_decode_i8: NULL pointer");
-    const int64_t cache = max_len * Hkv * D, kvb = kv_batch_pitch == 0 ? cache : kv_batch_pitch;   // (< 2^17 * 2^31 * 2^8)
-    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM, "asq_attn_decode_i8: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)",
-                (long long)Hq, (long long)Hkv, (long long)D);
-    ASQ_REQUIRE(kvb >= cache && kvb % 16 == 0 && kvb <= (1ll << 60) / B, ASQ_ERR_DIM, "asq_attn_decode_i8: kv_batch_pitch must be 0 (dense) or >= max_len * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_cache) | ((uintptr_t)v_cache) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN, "asq_attn_decode_i8: q, the caches and out must be 16-B aligned");
-    ASQ_REQUIRE(((uintptr_t)kv_len & 3) == 0, ASQ_ERR_ALIGN, "asq_attn_decode_i8: kv_len must be 4-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int r = (int)(Hq / Hkv);
-    const DecArgs a{q, k_cache, v_cache, kv_len, out, kvb, (int)Hq, (int)Hkv, (int)D, r, (int)max_len, dec_chunk(r, max_len), qk_alpha, pv_alpha};
-    int rc;
-    switch ((D + 63) / 64) {
-    case 1: rc = launch_decode<1>(a, grid, st); break;
-    case 2: rc = launch_decode<2>(a, grid, st); break;
-    case 3: rc = launch_decode<3>(a, grid, st); break;
-    default: rc = launch_decode<4>(a, grid, st); break;
-    }
-    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_decode_i8");
+    return attn_i8({"asq_attn_decode_i8", false, false, q, k_cache, v_cache, nullptr, kv_len, nullptr, out, B, 1, Hq, Hkv, D, max_len, kv_batch_pitch, {}, qk_alpha, pv_alpha}, stream);
 }
 
 extern "C" int asq_attn_decode_i8_paged(const int8_t *q, const int8_t *k_pool, const int8_t *v_pool, const int32_t *block_table, const int32_t *kv_len, int8_t *out, int64_t B,
                                         int64_t Hq, int64_t Hkv, int64_t D, int64_t num_pages, int64_t page_size, int64_t page_pitch, int64_t table_pitch, int64_t max_len,
                                         float qk_alpha, float pv_alpha, void *stream)
 {
-    const AsqRange range_("asq_attn_decode_i8_paged");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17) && num_pages >= 0 &&
-                    num_pages < lim && page_size >= 0 && page_size < lim && table_pitch >= 0 && table_pitch < lim,
-                ASQ_ERR_DIM, "asq_attn_decode_i8_paged: bad dims B=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld num_pages=%lld page_size=%lld table_pitch=%lld", (long long)B,
-                (long long)Hq, (long long)Hkv, (long long)D, (long long)max_len, (long long)num_pages, (long long)page_size, (long long)table_pitch);
-    int64_t grid = 0, qn = 0, page = 0;   // as asq_attn_decode_i8; a page holds page_size * Hkv * D bytes
-    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &grid) && grid < lim && !__builtin_mul_overflow(B * Hq, D, &qn) && !__builtin_mul_overflow(page_size * Hkv, D, &page) &&
-                    page <= (1ll << 60),
-                ASQ_ERR_DIM, "asq_attn_decode_i8_paged: dims overflow");
-    if (B == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k_pool && v_pool && block_table && out, ASQ_ERR_NULL, "asq_attn_decode_i8_paged: NULL pointer");
-    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM,
-                "asq_attn_decode_i8_paged: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)", (long long)Hq, (long long)Hkv, (long long)D);
-    const int64_t pp = page_pitch == 0 ? page : page_pitch;
-    ASQ_REQUIRE(page_size > 0 && page_size % 16 == 0, ASQ_ERR_DIM, "asq_attn_decode_i8_paged: page_size must be a positive multiple of 16, got %lld", (long long)page_size);
-    ASQ_REQUIRE(pp >= page && pp % 16 == 0 && pp <= (1ll << 60) / (num_pages > 0 ? num_pages : 1), ASQ_ERR_DIM,
-                "asq_attn_decode_i8_paged: page_pitch must be 0 (dense) or >= page_size * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(max_len <= table_pitch * page_size, ASQ_ERR_DIM, "asq_attn_decode_i8_paged: max_len %lld needs more than the %lld table entries of %lld keys a sequence has",
-                (long long)max_len, (long long)table_pitch, (long long)page_size);
-    ASQ_REQUIRE(max_len == 0 || num_pages > 0, ASQ_ERR_DIM, "asq_attn_decode_i8_paged: max_len %lld with a pool of no pages", (long long)max_len);
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_pool) | ((uintptr_t)v_pool) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN,
-                "asq_attn_decode_i8_paged: q, the pools and out must be 16-B aligned");
-    ASQ_REQUIRE((((uintptr_t)kv_len | (uintptr_t)block_table) & 3) == 0, ASQ_ERR_ALIGN, "asq_attn_decode_i8_paged: kv_len and block_table must be 4-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int r = (int)(Hq / Hkv);
-    const DecPagedArgs a{{q, k_pool, v_pool, kv_len, out, pp, (int)Hq, (int)Hkv, (int)D, r, (int)max_len, dec_chunk(r, max_len), qk_alpha, pv_alpha},
-                         block_table, table_pitch, (int)num_pages, (int)page_size};
-    int rc;
-    switch ((D + 63) / 64) {
-    case 1: rc = launch_decode<1, true>(a, grid, st); break;
-    case 2: rc = launch_decode<2, true>(a, grid, st); break;
-    case 3: rc = launch_decode<3, true>(a, grid, st); break;
-    default: rc = launch_decode<4, true>(a, grid, st); break;
-    }
-    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_decode_i8_paged");
+    return attn_i8({"asq_attn_decode_i8_paged", true, false, q, k_pool, v_pool, block_table, kv_len, nullptr, out, B, 1, Hq, Hkv, D, max_len, 0,
+                    {num_pages, page_size, page_pitch, table_pitch}, qk_alpha, pv_alpha},
+                   stream);
 }
 
 // ---- include/asq_hip_extend.h: Sq query tokens per sequence under a causal mask (the MULTI forms) ----------------------------------------------------------------
 extern "C" int asq_attn_extend_i8(const int8_t *q, const int8_t *k_cache, const int8_t *v_cache, const int32_t *kv_len, const int32_t *q_len, int8_t *out, int64_t B,
                                   int64_t Sq, int64_t Hq, int64_t Hkv, int64_t D, int64_t kv_batch_pitch, int64_t max_len, float qk_alpha, float pv_alpha, void *stream)
 {
-    const AsqRange range_("asq_attn_extend_i8");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && Sq >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Sq < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17),
-                ASQ_ERR_DIM, "asq_attn_extend_i8: bad dims B=%lld Sq=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld", (long long)B, (long long)Sq, (long long)Hq, (long long)Hkv,
-                (long long)D, (long long)max_len);
-    int64_t bh = 0, grid = 0, qn = 0;   // B * Hkv (sequence, KV head) pairs; B * Sq * Hq * D bytes of q and out
-    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &bh) && bh < lim && !__builtin_mul_overflow(B * Sq, Hq, &qn) && !__builtin_mul_overflow(qn, D, &qn), ASQ_ERR_DIM,
-                "asq_attn_extend_i8: dims overflow");
-    if (B == 0 || Sq == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k_cache && v_cache && out, ASQ_ERR_NULL, "asq_attn_extend_i8: NULL pointer");
-    const int64_t cache = max_len * Hkv * D, kvb = kv_batch_pitch == 0 ? cache : kv_batch_pitch;   // (< 2^17 * 2^31 * 2^8)
-    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM, "asq_attn_extend_i8: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)",
-                (long long)Hq, (long long)Hkv, (long long)D);
-    const DecMulti m = dec_multi(q_len, Sq, (int)(Hq / Hkv));
-    ASQ_REQUIRE(!__builtin_mul_overflow(bh, (int64_t)m.groups, &grid) && grid < lim, ASQ_ERR_DIM, "asq_attn_extend_i8: %lld x %lld x %d workgroups do not fit a 31-bit grid",
-                (long long)B, (long long)Hkv, m.groups);
-    ASQ_REQUIRE(kvb >= cache && kvb % 16 == 0 && kvb <= (1ll << 60) / B, ASQ_ERR_DIM, "asq_attn_extend_i8: kv_batch_pitch must be 0 (dense) or >= max_len * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_cache) | ((uintptr_t)v_cache) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN, "asq_attn_extend_i8: q, the caches and out must be 16-B aligned");
-    ASQ_REQUIRE((((uintptr_t)kv_len | (uintptr_t)q_len) & 3) == 0, ASQ_ERR_ALIGN, "asq_attn_extend_i8: kv_len and q_len must be 4-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int R = m.hr * m.T;
-    const DecMultiArgs a{{q, k_cache, v_cache, kv_len, out, kvb, (int)Hq, (int)Hkv, (int)D, R, (int)max_len, dec_chunk(R, max_len), qk_alpha, pv_alpha}, m};
-    int rc;
-    switch ((D + 63) / 64) {
-    case 1: rc = launch_decode<1, false, true>(a, grid, st); break;
-    case 2: rc = launch_decode<2, false, true>(a, grid, st); break;
-    case 3: rc = launch_decode<3, false, true>(a, grid, st); break;
-    default: rc = launch_decode<4, false, true>(a, grid, st); break;
-    }
-    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_extend_i8");
+    return attn_i8({"asq_attn_extend_i8", false, true, q, k_cache, v_cache, nullptr, kv_len, q_len, out, B, Sq, Hq, Hkv, D, max_len, kv_batch_pitch, {}, qk_alpha, pv_alpha}, stream);
 }
 
 extern "C" int asq_attn_extend_i8_paged(const int8_t *q, const int8_t *k_pool, const int8_t *v_pool, const int32_t *block_table, const int32_t *kv_len, const int32_t *q_len,
                                         int8_t *out, int64_t B, int64_t Sq, int64_t Hq, int64_t Hkv, int64_t D, int64_t num_pages, int64_t page_size, int64_t page_pitch,
                                         int64_t table_pitch, int64_t max_len, float qk_alpha, float pv_alpha, void *stream)
 {
-    const AsqRange range_("asq_attn_extend_i8_paged");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && Sq >= 0 && Hq >= 0 && Hkv >= 0 && B < lim && Sq < lim && Hq < lim && Hkv < lim && D > 0 && D <= 256 && max_len >= 0 && max_len < (1ll << 17) &&
-                    num_pages >= 0 && num_pages < lim && page_size >= 0 && page_size < lim && table_pitch >= 0 && table_pitch < lim,
-                ASQ_ERR_DIM, "asq_attn_extend_i8_paged: bad dims B=%lld Sq=%lld Hq=%lld Hkv=%lld D=%lld max_len=%lld num_pages=%lld page_size=%lld table_pitch=%lld", (long long)B,
-                (long long)Sq, (long long)Hq, (long long)Hkv, (long long)D, (long long)max_len, (long long)num_pages, (long long)page_size, (long long)table_pitch);
-    int64_t bh = 0, grid = 0, qn = 0, page = 0;   // as asq_attn_extend_i8; a page holds page_size * Hkv * D bytes
-    ASQ_REQUIRE(!__builtin_mul_overflow(B, Hkv, &bh) && bh < lim && !__builtin_mul_overflow(B * Sq, Hq, &qn) && !__builtin_mul_overflow(qn, D, &qn) &&
-                    !__builtin_mul_overflow(page_size * Hkv, D, &page) && page <= (1ll << 60),
-                ASQ_ERR_DIM, "asq_attn_extend_i8_paged: dims overflow");
-    if (B == 0 || Sq == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k_pool && v_pool && block_table && out, ASQ_ERR_NULL, "asq_attn_extend_i8_paged: NULL pointer");
-    ASQ_REQUIRE(D % 16 == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, ASQ_ERR_DIM,
-                "asq_attn_extend_i8_paged: head_dim must be a multiple of 16 and Hq = r * Hkv with r <= 16 (Hq=%lld Hkv=%lld D=%lld)", (long long)Hq, (long long)Hkv, (long long)D);
-    const DecMulti m = dec_multi(q_len, Sq, (int)(Hq / Hkv));
-    ASQ_REQUIRE(!__builtin_mul_overflow(bh, (int64_t)m.groups, &grid) && grid < lim, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: %lld x %lld x %d workgroups do not fit a 31-bit grid",
-                (long long)B, (long long)Hkv, m.groups);
-    const int64_t pp = page_pitch == 0 ? page : page_pitch;
-    ASQ_REQUIRE(page_size > 0 && page_size % 16 == 0, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: page_size must be a positive multiple of 16, got %lld", (long long)page_size);
-    ASQ_REQUIRE(pp >= page && pp % 16 == 0 && pp <= (1ll << 60) / (num_pages > 0 ? num_pages : 1), ASQ_ERR_DIM,
-                "asq_attn_extend_i8_paged: page_pitch must be 0 (dense) or >= page_size * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(max_len <= table_pitch * page_size, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: max_len %lld needs more than the %lld table entries of %lld keys a sequence has",
-                (long long)max_len, (long long)table_pitch, (long long)page_size);
-    ASQ_REQUIRE(max_len == 0 || num_pages > 0, ASQ_ERR_DIM, "asq_attn_extend_i8_paged: max_len %lld with a pool of no pages", (long long)max_len);
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k_pool) | ((uintptr_t)v_pool) | ((uintptr_t)out)) & 15) == 0, ASQ_ERR_ALIGN,
-                "asq_attn_extend_i8_paged: q, the pools and out must be 16-B aligned");
-    ASQ_REQUIRE((((uintptr_t)kv_len | (uintptr_t)q_len | (uintptr_t)block_table) & 3) == 0, ASQ_ERR_ALIGN,
-                "asq_attn_extend_i8_paged: kv_len, q_len and block_table must be 4-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int R = m.hr * m.T;
-    DecMultiPagedArgs a{};
-    static_cast<DecPagedArgs &>(a) = DecPagedArgs{{q, k_pool, v_pool, kv_len, out, pp, (int)Hq, (int)Hkv, (int)D, R, (int)max_len, dec_chunk(R, max_len), qk_alpha, pv_alpha},
-                                                  block_table, table_pitch, (int)num_pages, (int)page_size};
-    a.m = m;
-    int rc;
-    switch ((D + 63) / 64) {
-    case 1: rc = launch_decode<1, true, true>(a, grid, st); break;
-    case 2: rc = launch_decode<2, true, true>(a, grid, st); break;
-    case 3: rc = launch_decode<3, true, true>(a, grid, st); break;
-    default: rc = launch_decode<4, true, true>(a, grid, st); break;
-    }
-    return rc != ASQ_OK ? rc : asq_after_launch(st, "asq_attn_extend_i8_paged");
+    return attn_i8({"asq_attn_extend_i8_paged", true, true, q, k_pool, v_pool, block_table, kv_len, q_len, out, B, Sq, Hq, Hkv, D, max_len, 0,
+                    {num_pages, page_size, page_pitch, table_pitch}, qk_alpha, pv_alpha},
+                   stream);
 }

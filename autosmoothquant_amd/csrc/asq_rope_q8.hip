@@ -14,6 +14,7 @@
 // as cache row; a token outside the tables or the cache writes no cache byte and a zero q8 row.
 #include "asq_quant_core.h"
 #include "asq_rope_core.h"
+#include "asq_paged.h"
 #include "../../include/asq_hip_attn.h"
 #include "../../include/asq_hip_decode.h"
 #include "../../include/asq_hip_paged.h"
@@ -123,25 +124,97 @@ __global__ void __launch_bounds__(256) rope_q8_kernel(const std::conditional_t<P
     store_q8<DT>(o + D / 2, o2);
 }
 
-template <int DT> static void launch_rope_q8(const RopeQ8Args &a, hipStream_t s)
+// Args: the argument struct of the (AT, PAGED) form
+template <int DT, bool AT, bool PAGED, class Args> static void launch_rope_q8(const Args &a, hipStream_t s)
 {
     const unsigned blocks = (unsigned)((a.nwork + 255) / 256);
-    if (a.nwork + 255 < (1ll << 32)) hipLaunchKernelGGL((rope_q8_kernel<DT, uint32_t>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((rope_q8_kernel<DT, uint64_t>), dim3(blocks), dim3(256), 0, s, a);
+    if (a.nwork + 255 < (1ll << 32)) hipLaunchKernelGGL((rope_q8_kernel<DT, uint32_t, AT, PAGED>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((rope_q8_kernel<DT, uint64_t, AT, PAGED>), dim3(blocks), dim3(256), 0, s, a);
 }
 
-template <int DT> static void launch_rope_q8_at(const RopeQ8AtArgs &a, hipStream_t s)
-{
-    const unsigned blocks = (unsigned)((a.nwork + 255) / 256);
-    if (a.nwork + 255 < (1ll << 32)) hipLaunchKernelGGL((rope_q8_kernel<DT, uint32_t, true>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((rope_q8_kernel<DT, uint64_t, true>), dim3(blocks), dim3(256), 0, s, a);
-}
+// ---- the host side, once for the three entries ("how an entry of this family is put together") --------------------------------------------------
+// What an append was called with.  The inputs are common; `dest` says where k and v go and which of the fields behind it count.  A new rule goes into rope_q8 below.
+enum RopeQ8Dest {
+    ROPE_Q8_SLOT,    // asq_rope_quantize_qkv: S rows from k8 / v8, positions pos0 .. pos0 + S - 1
+    ROPE_Q8_CACHE,   // asq_rope_quantize_qkv_at: row pos[b] + s of sequence b of [B, max_len, Hkv, D] caches
+    ROPE_Q8_POOL,    // asq_rope_quantize_qkv_paged: the same row, in the page the block table names
+};
+struct RopeQ8Call {
+    const char *what;   // the entry's name, in every error text
+    RopeQ8Dest dest;
+    const void *q, *k, *v;
+    int64_t q_pitch, k_pitch, v_pitch;
+    int x_dtype;
+    const void *cos_tab, *sin_tab;
+    int64_t tab_rows;
+    int8_t *q8, *k8, *v8;   // k8 / v8: the slot, the caches' bases or the pools' bases
+    float q_scale, k_scale, v_scale;
+    int64_t B, S, Hq, Hkv, D;
+    int64_t pos0;             // slot
+    const int32_t *pos;       // cache, pool
+    int64_t max_len;          // cache, pool
+    int64_t kv_batch_pitch;   // slot, cache: as given (0: dense)
+    const int32_t *table;     // pool
+    AsqPaged pg;              // pool: num_pages, page_size, page_pitch, table_pitch as given
+};
 
-template <int DT> static void launch_rope_q8_paged(const RopeQ8PagedArgs &a, hipStream_t s)
+// The rules of a call in the order the headers state -- dims and overflow, the dtype, nothing to do, NULL, the shape rules, 16-B then 4-B alignment -- then the kernel
+// arguments and the launch.
+static int rope_q8(RopeQ8Call c, void *stream)
 {
-    const unsigned blocks = (unsigned)((a.nwork + 255) / 256);
-    if (a.nwork + 255 < (1ll << 32)) hipLaunchKernelGGL((rope_q8_kernel<DT, uint32_t, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((rope_q8_kernel<DT, uint64_t, true, true>), dim3(blocks), dim3(256), 0, s, a);
+    const AsqRange range_(c.what);
+    const int64_t lim = 1ll << 31;
+    const bool slot = c.dest == ROPE_Q8_SLOT, pool = c.dest == ROPE_Q8_POOL;
+    const int64_t B = c.B, S = c.S, Hq = c.Hq, Hkv = c.Hkv, D = c.D;
+    ASQ_REQUIRE(B >= 0 && S >= 0 && Hq >= 0 && Hkv >= 0 && D > 0 && B < lim && S < lim && Hq < lim && Hkv < lim && Hq + 2 * Hkv < lim && D < (1ll << 20) && c.tab_rows >= 0 &&
+                    c.tab_rows < (1ll << 40) && (slot ? c.pos0 >= 0 && c.pos0 < (1ll << 40) : c.max_len >= 0 && c.max_len < lim),
+                ASQ_ERR_DIM, "%s: bad dims", c.what);
+    // B * S * (Hq + 2 Hkv) * D elements in all; at most nelem / 8 threads, in blocks of 256 on a 31-bit grid.  rows: the bytes a sequence holds in k8 / v8 -- a cache's
+    // max_len * Hkv * D here, a slot's S * Hkv * D (within nelem) below
+    int64_t heads = 0, nelem = 0, rows = 0;
+    ASQ_REQUIRE(!__builtin_mul_overflow(B * S, Hq + 2 * Hkv, &heads) && !__builtin_mul_overflow(heads, D, &nelem) && nelem < (1ll << 41) &&
+                    (c.dest != ROPE_Q8_CACHE || (!__builtin_mul_overflow(c.max_len * Hkv, D, &rows) && rows <= (1ll << 60))),
+                ASQ_ERR_DIM, "%s: dims overflow", c.what);
+    if (pool)
+        if (const int rc = c.pg.dims(c.what, Hkv, D)) return rc;
+    ASQ_REQUIRE(c.x_dtype == ASQ_F32 || c.x_dtype == ASQ_F16 || c.x_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "%s: bad x_dtype %d", c.what, c.x_dtype);
+    if (B == 0 || S == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
+    ASQ_REQUIRE(c.q && c.k && c.v && c.cos_tab && c.sin_tab && c.q8 && c.k8 && c.v8 && (slot || c.pos) && (!pool || c.table), ASQ_ERR_NULL, "%s: NULL pointer", c.what);
+    const int vec = c.x_dtype == ASQ_F32 ? 4 : 8;
+    ASQ_REQUIRE(D % (2 * vec) == 0, ASQ_ERR_DIM, "%s: head_dim must be a multiple of %d", c.what, 2 * vec);
+    const int64_t qld = c.q_pitch == 0 ? Hq * D : c.q_pitch, kld = c.k_pitch == 0 ? Hkv * D : c.k_pitch, vld = c.v_pitch == 0 ? Hkv * D : c.v_pitch;
+    ASQ_REQUIRE(qld >= Hq * D && kld >= Hkv * D && vld >= Hkv * D && qld % vec == 0 && kld % vec == 0 && vld % vec == 0 &&
+                    (qld > kld ? (qld > vld ? qld : vld) : (kld > vld ? kld : vld)) <= (1ll << 60) / (B * S),
+                ASQ_ERR_DIM, "%s: a row pitch must be 0 (dense) or >= H * D and a multiple of %d elements", c.what, vec);
+    int64_t pitch;   // bytes between sequences of k8 / v8, or between pages of the pools
+    if (pool) {
+        if (const int rc = c.pg.shape(c.what, c.max_len)) return rc;
+        pitch = c.pg.pitch();
+    } else {
+        if (slot) rows = S * Hkv * D;
+        pitch = c.kv_batch_pitch == 0 ? rows : c.kv_batch_pitch;
+        ASQ_REQUIRE(pitch >= rows && pitch % 16 == 0 && pitch <= (1ll << 60) / B, ASQ_ERR_DIM, "%s: kv_batch_pitch must be 0 (dense) or >= %s * Hkv * D and a multiple of 16", c.what,
+                    slot ? "S" : "max_len");
+    }
+    ASQ_REQUIRE(!slot || S <= c.tab_rows - c.pos0, ASQ_ERR_DIM, "%s: positions %lld .. %lld need more than the %lld rows of cos_tab / sin_tab", c.what, (long long)c.pos0,
+                (long long)(c.pos0 + S - 1), (long long)c.tab_rows);
+    ASQ_REQUIRE(((((uintptr_t)c.q) | ((uintptr_t)c.k) | ((uintptr_t)c.v) | ((uintptr_t)c.cos_tab) | ((uintptr_t)c.sin_tab) | ((uintptr_t)c.q8) | ((uintptr_t)c.k8) | ((uintptr_t)c.v8)) & 15) == 0,
+                ASQ_ERR_ALIGN, "%s: pointers must be 16-B aligned", c.what);
+    ASQ_REQUIRE((((uintptr_t)c.pos | (uintptr_t)c.table) & 3) == 0, ASQ_ERR_ALIGN, "%s: %s must be 4-B aligned", c.what, pool ? "pos and block_table" : "pos");
+    hipStream_t st = (hipStream_t)stream;
+    const auto recip = [](float s) { return s > 0x1p-60f && s < 0x1p60f ? 1.0f / s : 0.0f; };   // asq_quantize_act's choice (quantize_dt): QDivFast inside, QDiv outside
+    const RopeQ8Args base{(const char *)c.q, (const char *)c.k, (const char *)c.v, (const char *)c.cos_tab, (const char *)c.sin_tab, c.q8, c.k8, c.v8, qld, kld, vld, pitch,
+                          slot ? c.pos0 : 0, heads * (D / 2 / vec), c.q_scale, recip(c.q_scale), c.k_scale, recip(c.k_scale), c.v_scale, recip(c.v_scale), (int)S, (int)Hq,
+                          (int)Hkv, (int)D};
+    const RopeQ8AtArgs at{base, c.pos, c.tab_rows < c.max_len ? c.tab_rows : c.max_len};
+    const RopeQ8PagedArgs paged{at, c.table, c.pg.table_pitch, (int)c.pg.num_pages, (int)c.pg.page_size};
+    asq_dispatch_dt(c.x_dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (slot) launch_rope_q8<DT, false, false>(base, st);
+        else if (pool) launch_rope_q8<DT, true, true>(paged, st);
+        else launch_rope_q8<DT, true, false>(at, st);
+    });
+    return asq_after_launch(st, c.what);
 }
 
 }  // namespace asq
@@ -151,73 +224,18 @@ extern "C" int asq_rope_quantize_qkv(const void *q, const void *k, const void *v
                                      const void *sin_tab, int64_t tab_rows, int64_t pos0, int8_t *q8, int8_t *k8, int8_t *v8, int64_t kv_batch_pitch, float q_scale,
                                      float k_scale, float v_scale, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D, void *stream)
 {
-    const AsqRange range_("asq_rope_quantize_qkv");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && S >= 0 && Hq >= 0 && Hkv >= 0 && D > 0 && B < lim && S < lim && Hq < lim && Hkv < lim && Hq + 2 * Hkv < lim && D < (1ll << 20) && pos0 >= 0 &&
-                    tab_rows >= 0 && pos0 < (1ll << 40) && tab_rows < (1ll << 40),
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv: bad dims");
-    int64_t heads = 0, nelem = 0;   // B * S * (Hq + 2 Hkv) * D elements in all; at most nelem / 8 threads, in blocks of 256 on a 31-bit grid
-    ASQ_REQUIRE(!__builtin_mul_overflow(B * S, Hq + 2 * Hkv, &heads) && !__builtin_mul_overflow(heads, D, &nelem) && nelem < (1ll << 41), ASQ_ERR_DIM,
-                "asq_rope_quantize_qkv: dims overflow");
-    ASQ_REQUIRE(x_dtype == ASQ_F32 || x_dtype == ASQ_F16 || x_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_rope_quantize_qkv: bad x_dtype %d", x_dtype);
-    if (B == 0 || S == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k && v && cos_tab && sin_tab && q8 && k8 && v8, ASQ_ERR_NULL, "asq_rope_quantize_qkv: NULL pointer");
-    const int vec = x_dtype == ASQ_F32 ? 4 : 8;
-    ASQ_REQUIRE(D % (2 * vec) == 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv: head_dim must be a multiple of %d", 2 * vec);
-    const int64_t qld = q_pitch == 0 ? Hq * D : q_pitch, kld = k_pitch == 0 ? Hkv * D : k_pitch, vld = v_pitch == 0 ? Hkv * D : v_pitch;
-    ASQ_REQUIRE(qld >= Hq * D && kld >= Hkv * D && vld >= Hkv * D && qld % vec == 0 && kld % vec == 0 && vld % vec == 0 &&
-                    (qld > kld ? (qld > vld ? qld : vld) : (kld > vld ? kld : vld)) <= (1ll << 60) / (B * S),
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv: a row pitch must be 0 (dense) or >= H * D and a multiple of %d elements", vec);
-    const int64_t kvb = kv_batch_pitch == 0 ? S * Hkv * D : kv_batch_pitch;
-    ASQ_REQUIRE(kvb >= S * Hkv * D && kvb % 16 == 0 && kvb <= (1ll << 60) / B, ASQ_ERR_DIM,
-                "asq_rope_quantize_qkv: kv_batch_pitch must be 0 (dense) or >= S * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(S <= tab_rows - pos0, ASQ_ERR_DIM, "asq_rope_quantize_qkv: positions %lld .. %lld need more than the %lld rows of cos_tab / sin_tab", (long long)pos0,
-                (long long)(pos0 + S - 1), (long long)tab_rows);
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)cos_tab) | ((uintptr_t)sin_tab) | ((uintptr_t)q8) | ((uintptr_t)k8) | ((uintptr_t)v8)) & 15) == 0,
-                ASQ_ERR_ALIGN, "asq_rope_quantize_qkv: pointers must be 16-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const auto recip = [](float s) { return s > 0x1p-60f && s < 0x1p60f ? 1.0f / s : 0.0f; };   // asq_quantize_act's choice (quantize_dt): QDivFast inside, QDiv outside
-    const RopeQ8Args a{(const char *)q, (const char *)k, (const char *)v, (const char *)cos_tab, (const char *)sin_tab, q8, k8, v8, qld, kld, vld, kvb, pos0,
-                       heads * (D / 2 / vec), q_scale, recip(q_scale), k_scale, recip(k_scale), v_scale, recip(v_scale), (int)S, (int)Hq, (int)Hkv, (int)D};
-    asq_dispatch_dt(x_dtype, [&](auto dt) { launch_rope_q8<decltype(dt)::value>(a, st); });
-    return asq_after_launch(st, "asq_rope_quantize_qkv");
+    return rope_q8({"asq_rope_quantize_qkv", ROPE_Q8_SLOT, q, k, v, q_pitch, k_pitch, v_pitch, x_dtype, cos_tab, sin_tab, tab_rows, q8, k8, v8, q_scale, k_scale, v_scale, B, S, Hq,
+                    Hkv, D, pos0, nullptr, 0, kv_batch_pitch, nullptr, {}},
+                   stream);
 }
 
 extern "C" int asq_rope_quantize_qkv_at(const void *q, const void *k, const void *v, int64_t q_pitch, int64_t k_pitch, int64_t v_pitch, int x_dtype, const void *cos_tab,
                                         const void *sin_tab, int64_t tab_rows, const int32_t *pos, int8_t *q8, int8_t *k_cache, int8_t *v_cache, int64_t kv_batch_pitch,
                                         int64_t max_len, float q_scale, float k_scale, float v_scale, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D, void *stream)
 {
-    const AsqRange range_("asq_rope_quantize_qkv_at");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && S >= 0 && Hq >= 0 && Hkv >= 0 && D > 0 && B < lim && S < lim && Hq < lim && Hkv < lim && Hq + 2 * Hkv < lim && D < (1ll << 20) && tab_rows >= 0 &&
-                    tab_rows < (1ll << 40) && max_len >= 0 && max_len < lim,
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv_at: bad dims");
-    int64_t heads = 0, nelem = 0, cache = 0;   // as asq_rope_quantize_qkv; a sequence of the caches holds max_len * Hkv * D bytes
-    ASQ_REQUIRE(!__builtin_mul_overflow(B * S, Hq + 2 * Hkv, &heads) && !__builtin_mul_overflow(heads, D, &nelem) && nelem < (1ll << 41) &&
-                    !__builtin_mul_overflow(max_len * Hkv, D, &cache) && cache <= (1ll << 60),
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv_at: dims overflow");
-    ASQ_REQUIRE(x_dtype == ASQ_F32 || x_dtype == ASQ_F16 || x_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_rope_quantize_qkv_at: bad x_dtype %d", x_dtype);
-    if (B == 0 || S == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k && v && cos_tab && sin_tab && pos && q8 && k_cache && v_cache, ASQ_ERR_NULL, "asq_rope_quantize_qkv_at: NULL pointer");
-    const int vec = x_dtype == ASQ_F32 ? 4 : 8;
-    ASQ_REQUIRE(D % (2 * vec) == 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_at: head_dim must be a multiple of %d", 2 * vec);
-    const int64_t qld = q_pitch == 0 ? Hq * D : q_pitch, kld = k_pitch == 0 ? Hkv * D : k_pitch, vld = v_pitch == 0 ? Hkv * D : v_pitch;
-    ASQ_REQUIRE(qld >= Hq * D && kld >= Hkv * D && vld >= Hkv * D && qld % vec == 0 && kld % vec == 0 && vld % vec == 0 &&
-                    (qld > kld ? (qld > vld ? qld : vld) : (kld > vld ? kld : vld)) <= (1ll << 60) / (B * S),
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv_at: a row pitch must be 0 (dense) or >= H * D and a multiple of %d elements", vec);
-    const int64_t kvb = kv_batch_pitch == 0 ? cache : kv_batch_pitch;
-    ASQ_REQUIRE(kvb >= cache && kvb % 16 == 0 && kvb <= (1ll << 60) / B, ASQ_ERR_DIM,
-                "asq_rope_quantize_qkv_at: kv_batch_pitch must be 0 (dense) or >= max_len * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)cos_tab) | ((uintptr_t)sin_tab) | ((uintptr_t)q8) | ((uintptr_t)k_cache) | ((uintptr_t)v_cache)) & 15) == 0,
-                ASQ_ERR_ALIGN, "asq_rope_quantize_qkv_at: pointers must be 16-B aligned");
-    ASQ_REQUIRE(((uintptr_t)pos & 3) == 0, ASQ_ERR_ALIGN, "asq_rope_quantize_qkv_at: pos must be 4-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const auto recip = [](float s) { return s > 0x1p-60f && s < 0x1p60f ? 1.0f / s : 0.0f; };   // asq_rope_quantize_qkv's choice
-    const RopeQ8AtArgs a{{(const char *)q, (const char *)k, (const char *)v, (const char *)cos_tab, (const char *)sin_tab, q8, k_cache, v_cache, qld, kld, vld, kvb, 0,
-                          heads * (D / 2 / vec), q_scale, recip(q_scale), k_scale, recip(k_scale), v_scale, recip(v_scale), (int)S, (int)Hq, (int)Hkv, (int)D},
-                         pos, tab_rows < max_len ? tab_rows : max_len};
-    asq_dispatch_dt(x_dtype, [&](auto dt) { launch_rope_q8_at<decltype(dt)::value>(a, st); });
-    return asq_after_launch(st, "asq_rope_quantize_qkv_at");
+    return rope_q8({"asq_rope_quantize_qkv_at", ROPE_Q8_CACHE, q, k, v, q_pitch, k_pitch, v_pitch, x_dtype, cos_tab, sin_tab, tab_rows, q8, k_cache, v_cache, q_scale, k_scale,
+                    v_scale, B, S, Hq, Hkv, D, 0, pos, max_len, kv_batch_pitch, nullptr, {}},
+                   stream);
 }
 
 extern "C" int asq_rope_quantize_qkv_paged(const void *q, const void *k, const void *v, int64_t q_pitch, int64_t k_pitch, int64_t v_pitch, int x_dtype, const void *cos_tab,
@@ -225,41 +243,7 @@ extern "C" int asq_rope_quantize_qkv_paged(const void *q, const void *k, const v
                                            int64_t num_pages, int64_t page_size, int64_t page_pitch, int64_t table_pitch, int64_t max_len, float q_scale, float k_scale,
                                            float v_scale, int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D, void *stream)
 {
-    const AsqRange range_("asq_rope_quantize_qkv_paged");
-    const int64_t lim = 1ll << 31;
-    ASQ_REQUIRE(B >= 0 && S >= 0 && Hq >= 0 && Hkv >= 0 && D > 0 && B < lim && S < lim && Hq < lim && Hkv < lim && Hq + 2 * Hkv < lim && D < (1ll << 20) && tab_rows >= 0 &&
-                    tab_rows < (1ll << 40) && max_len >= 0 && max_len < lim && num_pages >= 0 && num_pages < lim && page_size >= 0 && page_size < lim && table_pitch >= 0 &&
-                    table_pitch < lim,
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: bad dims");
-    int64_t heads = 0, nelem = 0, page = 0;   // as asq_rope_quantize_qkv; a page holds page_size * Hkv * D bytes
-    ASQ_REQUIRE(!__builtin_mul_overflow(B * S, Hq + 2 * Hkv, &heads) && !__builtin_mul_overflow(heads, D, &nelem) && nelem < (1ll << 41) &&
-                    !__builtin_mul_overflow(page_size * Hkv, D, &page) && page <= (1ll << 60),
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: dims overflow");
-    ASQ_REQUIRE(x_dtype == ASQ_F32 || x_dtype == ASQ_F16 || x_dtype == ASQ_BF16, ASQ_ERR_DTYPE, "asq_rope_quantize_qkv_paged: bad x_dtype %d", x_dtype);
-    if (B == 0 || S == 0 || Hq == 0 || Hkv == 0) return ASQ_OK;
-    ASQ_REQUIRE(q && k && v && cos_tab && sin_tab && pos && block_table && q8 && k_pool && v_pool, ASQ_ERR_NULL, "asq_rope_quantize_qkv_paged: NULL pointer");
-    const int vec = x_dtype == ASQ_F32 ? 4 : 8;
-    ASQ_REQUIRE(D % (2 * vec) == 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: head_dim must be a multiple of %d", 2 * vec);
-    const int64_t qld = q_pitch == 0 ? Hq * D : q_pitch, kld = k_pitch == 0 ? Hkv * D : k_pitch, vld = v_pitch == 0 ? Hkv * D : v_pitch;
-    ASQ_REQUIRE(qld >= Hq * D && kld >= Hkv * D && vld >= Hkv * D && qld % vec == 0 && kld % vec == 0 && vld % vec == 0 &&
-                    (qld > kld ? (qld > vld ? qld : vld) : (kld > vld ? kld : vld)) <= (1ll << 60) / (B * S),
-                ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: a row pitch must be 0 (dense) or >= H * D and a multiple of %d elements", vec);
-    const int64_t pp = page_pitch == 0 ? page : page_pitch;
-    ASQ_REQUIRE(page_size > 0 && page_size % 16 == 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: page_size must be a positive multiple of 16, got %lld", (long long)page_size);
-    ASQ_REQUIRE(pp >= page && pp % 16 == 0 && pp <= (1ll << 60) / (num_pages > 0 ? num_pages : 1), ASQ_ERR_DIM,
-                "asq_rope_quantize_qkv_paged: page_pitch must be 0 (dense) or >= page_size * Hkv * D and a multiple of 16");
-    ASQ_REQUIRE(max_len <= table_pitch * page_size, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: max_len %lld needs more than the %lld table entries of %lld rows a sequence has",
-                (long long)max_len, (long long)table_pitch, (long long)page_size);
-    ASQ_REQUIRE(max_len == 0 || num_pages > 0, ASQ_ERR_DIM, "asq_rope_quantize_qkv_paged: max_len %lld with a pool of no pages", (long long)max_len);
-    ASQ_REQUIRE(((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)cos_tab) | ((uintptr_t)sin_tab) | ((uintptr_t)q8) | ((uintptr_t)k_pool) | ((uintptr_t)v_pool)) & 15) == 0,
-                ASQ_ERR_ALIGN, "asq_rope_quantize_qkv_paged: pointers must be 16-B aligned");
-    ASQ_REQUIRE((((uintptr_t)pos | (uintptr_t)block_table) & 3) == 0, ASQ_ERR_ALIGN, "asq_rope_quantize_qkv_paged: pos and block_table must be 4-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const auto recip = [](float s) { return s > 0x1p-60f && s < 0x1p60f ? 1.0f / s : 0.0f; };   // asq_rope_quantize_qkv's choice
-    const RopeQ8PagedArgs a{{{(const char *)q, (const char *)k, (const char *)v, (const char *)cos_tab, (const char *)sin_tab, q8, k_pool, v_pool, qld, kld, vld, pp, 0,
-                              heads * (D / 2 / vec), q_scale, recip(q_scale), k_scale, recip(k_scale), v_scale, recip(v_scale), (int)S, (int)Hq, (int)Hkv, (int)D},
-                             pos, tab_rows < max_len ? tab_rows : max_len},
-                            block_table, table_pitch, (int)num_pages, (int)page_size};
-    asq_dispatch_dt(x_dtype, [&](auto dt) { launch_rope_q8_paged<decltype(dt)::value>(a, st); });
-    return asq_after_launch(st, "asq_rope_quantize_qkv_paged");
+    return rope_q8({"asq_rope_quantize_qkv_paged", ROPE_Q8_POOL, q, k, v, q_pitch, k_pitch, v_pitch, x_dtype, cos_tab, sin_tab, tab_rows, q8, k_pool, v_pool, q_scale, k_scale,
+                    v_scale, B, S, Hq, Hkv, D, 0, pos, max_len, 0, block_table, {num_pages, page_size, page_pitch, table_pitch}},
+                   stream);
 }

@@ -28,6 +28,12 @@ from ... import ops
 from .bmm import BMM_S8T_S8N_S8T, BMM_S8T_S8N_SOFTMAX_S8T
 
 
+def _q8_tokens(q8, one):
+    """q8 of Int8Attention's cache methods is the append's [B, Sq, Hq, d] (one: a decode step, Sq = 1); the ops check the rest"""
+    if not torch.is_tensor(q8) or q8.dim() != 4 or (one and q8.shape[1] != 1):
+        raise ValueError(f"q8 must be [B, {1 if one else 'Sq'}, Hq, d], got {list(getattr(q8, 'shape', []))}")
+
+
 class Int8Attention(torch.nn.Module):
     def __init__(self, qk_alpha=1.0, pv_alpha=1.0, causal=True):
         super().__init__()
@@ -115,17 +121,14 @@ class Int8Attention(torch.nn.Module):
         each) with qk_bmm's and pv_bmm's alphas.  A decode step sees every key it is given, so the causal flag does not apply.  max_len: a bound on the lengths
         (cache.bound()), the caches' rows when absent.  With few sequences x KV heads (a single sequence) the launch leaves most of the chip idle: forward(layout=
         "bshd") remains the route there."""
-        if not torch.is_tensor(q8) or q8.dim() != 4 or q8.shape[1] != 1:
-            raise ValueError(f"q8 must be [B, 1, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        _q8_tokens(q8, one=True)
         return ops.attn_decode_i8(q8, k_cache, v_cache, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), max_len=max_len)
-
 
     def decode_paged(self, q8, k_pool, v_pool, block_table, kv_len=None, max_len=None):
         """decode on a paged cache, ONE launch (ops.attn_decode_i8_paged): q8 int8 [B, 1, Hq, d] -> [B, 1, Hq, d] over k_pool / v_pool [num_pages, page_size, Hkv, d]
         (a PagedInt8KVCache's k and v), key n of sequence b in page block_table[b, n // page_size] (int32 [B, T] on the device).  kv_len and max_len as in decode
         (max_len: T * page_size when absent).  The output bytes are decode's on a contiguous cache holding the same keys."""
-        if not torch.is_tensor(q8) or q8.dim() != 4 or q8.shape[1] != 1:
-            raise ValueError(f"q8 must be [B, 1, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        _q8_tokens(q8, one=True)
         return ops.attn_decode_i8_paged(q8, k_pool, v_pool, block_table, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), max_len=max_len)
 
     def extend(self, q8, k_cache, v_cache, kv_len=None, q_len=None, max_len=None):
@@ -134,15 +137,13 @@ class Int8Attention(torch.nn.Module):
         token s sits at key position kv_len[b] - q_len[b] + s and sees the keys up to and including its own; padded tokens get zero rows.  The verification of draft
         tokens (followed by cache.rewind of the rejected ones), a prompt chunk, a mixed batch.  With Sq * r <= 16 the step costs about one decode launch; a long prefill
         stays with forward(layout="bshd")."""
-        if not torch.is_tensor(q8) or q8.dim() != 4:
-            raise ValueError(f"q8 must be [B, Sq, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        _q8_tokens(q8, one=False)
         return ops.attn_extend_i8(q8, k_cache, v_cache, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), q_len=q_len, max_len=max_len)
 
     def extend_paged(self, q8, k_pool, v_pool, block_table, kv_len=None, q_len=None, max_len=None):
         """extend on a paged cache, ONE launch (ops.attn_extend_i8_paged): the pools and the table as in decode_paged, q8, q_len and the per-token rule as in extend.  The
         output bytes are extend's on a contiguous cache holding the same keys."""
-        if not torch.is_tensor(q8) or q8.dim() != 4:
-            raise ValueError(f"q8 must be [B, Sq, Hq, d], got {list(getattr(q8, 'shape', []))}")
+        _q8_tokens(q8, one=False)
         return ops.attn_extend_i8_paged(q8, k_pool, v_pool, block_table, kv_len, self.qk_bmm._alpha(), self.pv_bmm._alpha(), q_len=q_len, max_len=max_len)
 
 
@@ -177,7 +178,53 @@ class Int8KVCache:
         self.length = 0
 
 
-class RaggedInt8KVCache:
+class _SequenceLengths:
+    """The length bookkeeping RaggedInt8KVCache and PagedInt8KVCache share: `kv_len` int32 [batch] on the cache's device -- allocated once and only written in place by
+    stream-ordered ops, so a captured step replays as the lengths move -- and its host mirror `lengths`, a list of ints, which serves every bounds check (ValueError, no
+    device sync).  `max_len`, the rows a sequence can hold, is the subclass's.  A step S is an int (every sequence) or one int per sequence.  _steps checks and changes
+    nothing, so a caller that runs its checks before _move keeps "a refused call changes no state"."""
+
+    def _init_lengths(self, batch, device):
+        self.kv_len = torch.zeros((batch,), dtype=torch.int32, device=device)
+        self.lengths = [0] * batch
+
+    def _steps(self, S, who, back=False):
+        """S as a list of ints; ValueError under `who`'s name for a wrong count, a negative step and one beyond max_len (back: beyond the sequence's length)"""
+        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
+        if len(steps) != len(self.lengths) or any(s < 0 or (s > n if back else n + s > self.max_len) for s, n in zip(steps, self.lengths)):
+            if back:
+                raise ValueError(f"{who}: {steps} tokens cannot be taken back from {len(self.lengths)} sequences of lengths {self.lengths}")
+            raise ValueError(f"{who}: {steps} more tokens after {self.lengths} do not fit {len(self.lengths)} sequences of max_len {self.max_len}")
+        return steps
+
+    def _move(self, S, steps, back=False):
+        """lengths += steps (back: -=): one stream-ordered add_ (sub_) on kv_len -- of the int S as the caller gave it, else of the steps sent over without a sync"""
+        delta = S if isinstance(S, int) else torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True)
+        if back:
+            self.kv_len.sub_(delta)
+            self.lengths = [n - s for n, s in zip(self.lengths, steps)]
+        else:
+            self.kv_len.add_(delta)
+            self.lengths = [n + s for n, s in zip(self.lengths, steps)]
+
+    def _reset_lengths(self, b):
+        """sequence b, or with None every sequence, back to length 0 -> the indices reset"""
+        if b is None:
+            self.kv_len.zero_()
+            seqs = range(len(self.lengths))
+        else:
+            b = range(len(self.lengths))[b]   # (IndexError outside, a negative index counts from the end)
+            self.kv_len[b:b + 1].zero_()
+            seqs = (b,)
+        for i in seqs:
+            self.lengths[i] = 0
+        return seqs
+
+    def bound(self):
+        return max(self.lengths, default=0)
+
+
+class RaggedInt8KVCache(_SequenceLengths):
     """Int8KVCache with a length per sequence: k and v [B, Smax, Hkv, d], `kv_len` int32 [B] on the cache's device -- what the kernels read: the append position of
     ops.rope_quantize_qkv_at, the number of keys of ops.attn_decode_i8, so a captured step replays as the lengths move -- and its host mirror `lengths`, a list of
     ints, which serves the bounds checks (ValueError, no device sync).
@@ -188,51 +235,23 @@ class RaggedInt8KVCache:
     def __init__(self, batch, max_len, kv_heads, head_dim, device=None):
         self.k = torch.zeros((batch, max_len, kv_heads, head_dim), dtype=torch.int8, device=device)
         self.v = torch.zeros_like(self.k)
-        self.kv_len = torch.zeros((batch,), dtype=torch.int32, device=device)
-        self.lengths = [0] * batch
+        self._init_lengths(batch, device)
 
     @property
     def max_len(self):
         return self.k.shape[1]
 
-    def _steps(self, S):
-        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
-        if len(steps) != len(self.lengths) or any(s < 0 or n + s > self.max_len for s, n in zip(steps, self.lengths)):
-            raise ValueError(f"RaggedInt8KVCache: {steps} more tokens after {self.lengths} do not fit {len(self.lengths)} sequences of max_len {self.max_len}")
-        return steps
-
     def advance(self, S):
-        steps = self._steps(S)
-        if isinstance(S, int):
-            self.kv_len.add_(S)
-        else:
-            self.kv_len.add_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
-        self.lengths = [n + s for n, s in zip(self.lengths, steps)]
+        self._move(S, self._steps(S, "RaggedInt8KVCache"))
 
     def rewind(self, S):
-        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
-        if len(steps) != len(self.lengths) or any(s < 0 or s > n for s, n in zip(steps, self.lengths)):
-            raise ValueError(f"RaggedInt8KVCache: {steps} tokens cannot be taken back from {len(self.lengths)} sequences of lengths {self.lengths}")
-        if isinstance(S, int):
-            self.kv_len.sub_(S)
-        else:
-            self.kv_len.sub_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
-        self.lengths = [n - s for n, s in zip(self.lengths, steps)]
+        self._move(S, self._steps(S, "RaggedInt8KVCache", back=True), back=True)
 
     def reset(self, b=None):
-        if b is None:
-            self.kv_len.zero_()
-            self.lengths = [0] * len(self.lengths)
-        else:
-            b = range(len(self.lengths))[b]   # (IndexError outside, a negative index counts from the end)
-            self.kv_len[b:b + 1].zero_()
-            self.lengths[b] = 0
-
-    def bound(self):
-        return max(self.lengths, default=0)
+        self._reset_lengths(b)
 
 
-class PagedInt8KVCache:
+class PagedInt8KVCache(_SequenceLengths):
     """A paged int8 KV cache: pools k and v [num_pages, page_size, Hkv, d] (page_size a multiple of 16), `block_table` int32 [batch, ceil(max_len / page_size)] and
     `kv_len` int32 [batch] on the cache's device -- what ops.rope_quantize_qkv_paged and ops.attn_decode_i8_paged read; both are allocated once and only written in
     place, so a captured step keeps reading the same addresses -- and their host mirrors: `lengths`, the page list of every sequence `pages`, and the free list `free`
@@ -251,9 +270,8 @@ class PagedInt8KVCache:
         self.k = torch.zeros((num_pages, page_size, kv_heads, head_dim), dtype=torch.int8, device=device)
         self.v = torch.zeros_like(self.k)
         self.block_table = torch.zeros((batch, -(-max_len // page_size)), dtype=torch.int32, device=device)
-        self.kv_len = torch.zeros((batch,), dtype=torch.int32, device=device)
+        self._init_lengths(batch, device)
         self.max_len = max_len
-        self.lengths = [0] * batch
         self.pages = [[] for _ in range(batch)]
         self.free = list(range(num_pages - 1, -1, -1))   # a stack: pop() hands out page 0 first, a freed page next
 
@@ -261,14 +279,8 @@ class PagedInt8KVCache:
     def page_size(self):
         return self.k.shape[1]
 
-    def _steps(self, S, what):
-        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
-        if len(steps) != len(self.lengths) or any(s < 0 or n + s > self.max_len for s, n in zip(steps, self.lengths)):
-            raise ValueError(f"PagedInt8KVCache.{what}: {steps} more tokens after {self.lengths} do not fit {len(self.lengths)} sequences of max_len {self.max_len}")
-        return steps
-
     def reserve(self, S):
-        steps = self._steps(S, "reserve")
+        steps = self._steps(S, "PagedInt8KVCache.reserve")
         need = [max(0, -(-(n + s) // self.page_size) - len(pg)) for n, s, pg in zip(self.lengths, steps, self.pages)]
         if sum(need) > len(self.free):
             raise ValueError(f"PagedInt8KVCache.reserve: {steps} more tokens after {self.lengths} need {sum(need)} more pages, {len(self.free)} are free")
@@ -290,40 +302,19 @@ class PagedInt8KVCache:
                 self.free.append(pg.pop())
 
     def advance(self, S):
-        steps = self._steps(S, "advance")
+        steps = self._steps(S, "PagedInt8KVCache.advance")
         if any(n + s > len(pg) * self.page_size for n, s, pg in zip(self.lengths, steps, self.pages)):
             raise ValueError(f"PagedInt8KVCache.advance: {steps} more tokens after {self.lengths} go beyond the reserved pages {[len(pg) for pg in self.pages]}")
-        if isinstance(S, int):
-            self.kv_len.add_(S)
-        else:
-            self.kv_len.add_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
-        self.lengths = [n + s for n, s in zip(self.lengths, steps)]
+        self._move(S, steps)
 
     def rewind(self, S):
-        steps = [S] * len(self.lengths) if isinstance(S, int) else [int(s) for s in S]
-        if len(steps) != len(self.lengths) or any(s < 0 or s > n for s, n in zip(steps, self.lengths)):
-            raise ValueError(f"PagedInt8KVCache.rewind: {steps} tokens cannot be taken back from {len(self.lengths)} sequences of lengths {self.lengths}")
-        if isinstance(S, int):
-            self.kv_len.sub_(S)
-        else:
-            self.kv_len.sub_(torch.tensor(steps, dtype=torch.int32).to(self.kv_len.device, non_blocking=True))
-        self.lengths = [n - s for n, s in zip(self.lengths, steps)]
+        self._move(S, self._steps(S, "PagedInt8KVCache.rewind", back=True), back=True)
         self._unreserve([-(-n // self.page_size) for n in self.lengths])
 
     def reset(self, b=None):
-        if b is None:
-            self.kv_len.zero_()
-            seqs = range(len(self.lengths))
-        else:
-            b = range(len(self.lengths))[b]   # (IndexError outside, a negative index counts from the end)
-            self.kv_len[b:b + 1].zero_()
-            seqs = (b,)
-        for i in seqs:
+        for i in self._reset_lengths(b):
             self.free.extend(reversed(self.pages[i]))
-            self.pages[i], self.lengths[i] = [], 0
-
-    def bound(self):
-        return max(self.lengths, default=0)
+            self.pages[i] = []
 
     def gather(self, b):
         n = self.lengths[b]
@@ -382,14 +373,14 @@ class RopeQuantQKV(torch.nn.Module):
             return ops.rope_quantize_qkv(q, k, v, cos, sin, qs, ks, vs, pos=pos)
         S = q.shape[1] if torch.is_tensor(q) and q.dim() == 4 else 0
         if isinstance(cache, RaggedInt8KVCache):
-            cache._steps(S)                                     # the S written rows fit every sequence ...
-            steps = cache._steps(S if advance is None else advance)   # ... and so does what the cache advances by (ValueError before anything is launched)
+            cache._steps(S, "RaggedInt8KVCache")                # the S written rows fit every sequence ...
+            steps = cache._steps(S if advance is None else advance, "RaggedInt8KVCache")   # ... and so does what the cache advances by (ValueError before anything is launched)
             q8, _, _ = ops.rope_quantize_qkv_at(q, k, v, cos, sin, qs, ks, vs, cache.kv_len, cache.k, cache.v)
             cache.advance(S if advance is None else steps)
             return q8, cache.k, cache.v
         if isinstance(cache, PagedInt8KVCache):
-            cache._steps(S, "reserve")
-            steps = cache._steps(S if advance is None else advance, "advance")
+            cache._steps(S, "PagedInt8KVCache.reserve")
+            steps = cache._steps(S if advance is None else advance, "PagedInt8KVCache.advance")
             if any(a > S for a in steps):
                 raise ValueError(f"PagedInt8KVCache: advance {steps} goes beyond the {S} rows written")
             held = [len(pg) for pg in cache.pages]

@@ -733,6 +733,76 @@ def _kv_slot(t, name, shape):
     return st[0] if B > 1 else 0
 
 
+# ---- the int8 KV-cache family: three appends (rope_quantize_qkv, _at, _paged) over one body, _qkv_append, and four attention ops (attn_decode_i8, attn_extend_i8 and
+# ---- their _paged forms) over another, _attn_i8.  A body is the shape rules in the ops' stated order (ValueError), then the devices (RuntimeError: no CPU fallback),
+# ---- the output and the launch; a rule of the family stands once, in a body or in a helper the two share, and a new rule or form goes there.  The bodies are flat on
+# ---- purpose: a decode step pays them once per layer (tools/pyoverhead.py times the seven ops).
+def _len_vec(t, name, B, optional=True):
+    """The shape rule of pos, kv_len and q_len: an int32 [B] tensor (optional: or None).  Its device comes after the op's other shape rules (_dev); the host never reads it."""
+    if (t is not None or not optional) and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,)):
+        raise ValueError(f"{name} must be {'None or ' if optional else ''}an int32 [{B}] tensor, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+
+
+def _qkv_append(entry, dest, q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, k8, v8, table=None, max_len=None):
+    """The three appends -> (q8, k8, v8).  q [B, S, Hq, D], k and v [B, S, Hkv, D] of one float dtype, each with its own row pitch (_bshd_pitch); cos / sin [T, D/2].  Where
+    k and v go is `dest`: "slot" -- pos an int, k8 / v8 a slot (_kv_slot; None: fresh dense tensors) at table rows pos .. pos + S - 1; "cache" -- pos an int32 [B]
+    vector, k8 / v8 the caches (_kv_caches); "pool" -- the same pos, k8 / v8 the pools behind the block table (_kv_pools, _block_table, max_len rows per sequence)."""
+    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
+    B, S, Hq, D = q.shape
+    dt, ks = q.dtype, k.shape   # (read once: every .shape builds a torch.Size)
+    Hkv = ks[2]
+    if k.dtype != dt or v.dtype != dt or ks != v.shape or tuple(ks) != (B, S, Hkv, D):
+        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
+    slot, paged = dest == "slot", dest == "pool"
+    cs = cos.shape if isinstance(cos, torch.Tensor) and isinstance(sin, torch.Tensor) else ()
+    if D % 2 or len(cs) != 2 or sin.shape != cs or cs[1] != D // 2 or (slot and (pos < 0 or cs[0] < pos + S)):
+        reach = f" with T >= pos + S = {pos + S} (pos {pos})" if slot else ""
+        raise ValueError(f"cos / sin must be [T, {D // 2}] tables{reach}, got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
+    T = cs[0]
+    if slot:
+        kn, vn, at, where = "k_out", "v_out", (pos,), (0,)
+        if (k8 is None) != (v8 is None):
+            raise ValueError("k_out and v_out come together")
+        if k8 is not None:
+            kvb, vb = _kv_slot(k8, kn, (B, S, Hkv, D)), _kv_slot(v8, vn, (B, S, Hkv, D))
+            if kvb != vb:
+                raise ValueError(f"k_out and v_out must have one common batch pitch, got {kvb} and {vb}")
+            where = (kvb,)
+    else:
+        if not paged:
+            kn, vn = "k_cache", "v_cache"
+            smax, _, kvb = _kv_caches(k8, v8, B, Hkv, D)
+            where = (kvb, smax)
+        else:
+            kn, vn = "k_pool", "v_pool"
+            num_pages, page_size, _, pitch = _kv_pools(k8, v8, Hkv, D)
+            tw, tp = _block_table(table, B)
+            max_len = tw * page_size if max_len is None else int(max_len)
+            if not 0 <= max_len <= tw * page_size:   # (an append has neither of the attention kernel's bounds: _attn_i8)
+                raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence")
+            where = (num_pages, page_size, pitch, tp, max_len)
+        _len_vec(pos, "pos", B, optional=False)
+        at = (pos.data_ptr(), table.data_ptr()) if paged else (pos.data_ptr(),)
+    _hip(q, "q"), _hip(k, "k"), _hip(v, "v")
+    fresh = k8 is None
+    if fresh:
+        k8, v8 = torch.empty((B, S, Hkv, D), dtype=torch.int8, device=q.device), torch.empty((B, S, Hkv, D), dtype=torch.int8, device=q.device)
+    else:
+        _hip(k8, kn), _hip(v8, vn)
+    if paged:
+        _hip(table, "block_table")
+    _operand(cos, "cos", dt, T * (D // 2)), _operand(sin, "sin", dt, T * (D // 2))
+    if not slot:
+        _dev(pos, "pos")
+    dev = _same_device(q, k, v, cos, sin, None if slot else pos, table if paged else None, k8, v8)
+    if not fresh:
+        _bump_version(k8), _bump_version(v8)
+    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
+    _launch(entry, dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[dt], cos.data_ptr(), sin.data_ptr(), T, *at, q8.data_ptr(), k8.data_ptr(),
+            v8.data_ptr(), *where, float(q_scale), float(k_scale), float(v_scale), B, S, Hq, Hkv, D, _stream(q))
+    return q8, k8, v8
+
+
 def rope_quantize_qkv(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos=0, k_out=None, v_out=None):
     """Rotary embedding of q and k at positions pos .. pos + S - 1, per-tensor int8 quantisation of q, k and v, and the write of k / v into a KV cache, in ONE launch
     (asq_rope_quantize_qkv) -> (q8, k8, v8).  q [B, S, Hq, D], k and v [B, S, Hkv, D] of one float dtype, each dense or a slice of a fused q || k || v output (rope's
@@ -741,54 +811,27 @@ def rope_quantize_qkv(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos=0, k_out
     returned as k8 / v8, nothing outside them is touched; otherwise fresh dense tensors.
     Every byte equals rope(x, cos[pos:pos + S], sin[pos:pos + S]) followed by quantize_act(., "per-tensor-div", scale) (v: the quantiser alone), by construction.
     Shapes and strides are checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
-    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
-    B, S, Hq, D = q.shape
-    Hkv = k.shape[2]
-    if k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or tuple(k.shape) != (B, S, Hkv, D):
-        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
-    pos = int(pos)
-    if (not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or D % 2 or cos.dim() != 2 or sin.shape != cos.shape or cos.shape[1] != D // 2 or pos < 0
-            or cos.shape[0] < pos + S):
-        raise ValueError(f"cos / sin must be [T, {D // 2}] tables with T >= pos + S = {pos + S} (pos {pos}), got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
-    T = cos.shape[0]
-    if (k_out is None) != (v_out is None):
-        raise ValueError("k_out and v_out come together")
-    kvb = 0
-    if k_out is not None:
-        kvb, vb = _kv_slot(k_out, "k_out", (B, S, Hkv, D)), _kv_slot(v_out, "v_out", (B, S, Hkv, D))
-        if kvb != vb:
-            raise ValueError(f"k_out and v_out must have one common batch pitch, got {kvb} and {vb}")
-    _hip(q, "q"), _hip(k, "k"), _hip(v, "v")
-    _operand(cos, "cos", q.dtype, T * (D // 2)), _operand(sin, "sin", q.dtype, T * (D // 2))
-    if k_out is None:
-        k8, v8 = torch.empty((B, S, Hkv, D), dtype=torch.int8, device=q.device), torch.empty((B, S, Hkv, D), dtype=torch.int8, device=q.device)
-    else:
-        k8, v8 = _hip(k_out, "k_out"), _hip(v_out, "v_out")
-        _bump_version(k8), _bump_version(v8)
-    dev = _same_device(q, k, v, cos, sin, k8, v8)
-    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
-    _launch("asq_rope_quantize_qkv", dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[q.dtype], cos.data_ptr(), sin.data_ptr(), T, pos,
-            q8.data_ptr(), k8.data_ptr(), v8.data_ptr(), kvb, float(q_scale), float(k_scale), float(v_scale), B, S, Hq, Hkv, D, _stream(q))
-    return q8, k8, v8
+    return _qkv_append("asq_rope_quantize_qkv", "slot", q, k, v, cos, sin, q_scale, k_scale, v_scale, int(pos), k_out, v_out)
 
 
 def _kv_cache(t, name, B, Hkv, D):
     """k_cache / v_cache of the ragged decode ops: an int8 [B, Smax, Hkv, D] tensor with strides (pitch, Hkv * D, D, 1) -- a cache, or a [:, :n] view of one -> (Smax,
     the batch pitch; 0: one sequence)"""
-    st = t.stride() if isinstance(t, torch.Tensor) and t.dim() == 4 else None
-    if (st is None or t.dtype != torch.int8 or t.shape[0] != B or (Hkv is not None and t.shape[2] != Hkv) or t.shape[3] != D or st[3] != 1 or st[2] != D
-            or (t.shape[1] > 1 and st[1] != t.shape[2] * D) or (B > 1 and (st[0] < t.shape[1] * t.shape[2] * D or st[0] % 16))):
+    sh, st = (t.shape, t.stride()) if isinstance(t, torch.Tensor) and t.dim() == 4 else (None, None)   # (read once: every t.shape builds a torch.Size)
+    if (st is None or t.dtype != torch.int8 or sh[0] != B or (Hkv is not None and sh[2] != Hkv) or sh[3] != D or st[3] != 1 or st[2] != D
+            or (sh[1] > 1 and st[1] != sh[2] * D) or (B > 1 and (st[0] < sh[1] * sh[2] * D or st[0] % 16))):
         raise ValueError(f"{name} must be an int8 [{B}, Smax, {'Hkv' if Hkv is None else Hkv}, {D}] cache (or a [:, :n] view of one) with strides (pitch, Hkv * D, D, 1), pitch >= Smax * Hkv * D "
                          f"and a multiple of 16, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))} with strides {st}")
-    return t.shape[1], (st[0] if B > 1 else 0)
+    return sh[1], (st[0] if B > 1 else 0)
 
 
 def _kv_caches(k_cache, v_cache, B, Hkv, D):
     """both caches of one shape and one pitch -> (Smax, Hkv, pitch)"""
     smax, pitch = _kv_cache(k_cache, "k_cache", B, Hkv, D)
-    if _kv_cache(v_cache, "v_cache", B, k_cache.shape[2], D) != (smax, pitch):
+    hkv = k_cache.shape[2]
+    if _kv_cache(v_cache, "v_cache", B, hkv, D) != (smax, pitch):
         raise ValueError(f"k_cache and v_cache must have one shape and one batch pitch, got {list(k_cache.shape)} {k_cache.stride()} and {list(v_cache.shape)} {v_cache.stride()}")
-    return smax, k_cache.shape[2], pitch
+    return smax, hkv, pitch
 
 
 def rope_quantize_qkv_at(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, k_cache, v_cache):
@@ -797,25 +840,7 @@ def rope_quantize_qkv_at(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, k_ca
     device (a captured step replays with moving positions).  k_cache / v_cache: int8 [B, Smax, Hkv, D] with strides (pitch, Hkv * D, D, 1) and one common pitch.
     A token with pos[b] < 0 or pos[b] + s >= min(T, Smax) writes nothing to the caches and gets a zero q8 row: the device checks, the host never reads pos.
     Every written byte equals rope_quantize_qkv called per sequence with pos = pos[b]."""
-    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
-    B, S, Hq, D = q.shape
-    Hkv = k.shape[2]
-    if k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or tuple(k.shape) != (B, S, Hkv, D):
-        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
-    if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or D % 2 or cos.dim() != 2 or sin.shape != cos.shape or cos.shape[1] != D // 2:
-        raise ValueError(f"cos / sin must be [T, {D // 2}] tables, got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
-    T = cos.shape[0]
-    smax, _, kvb = _kv_caches(k_cache, v_cache, B, Hkv, D)
-    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or tuple(pos.shape) != (B,):
-        raise ValueError(f"pos must be an int32 [{B}] tensor, got {getattr(pos, 'dtype', type(pos))} {list(getattr(pos, 'shape', []))}")
-    _hip(q, "q"), _hip(k, "k"), _hip(v, "v"), _hip(k_cache, "k_cache"), _hip(v_cache, "v_cache")
-    _operand(cos, "cos", q.dtype, T * (D // 2)), _operand(sin, "sin", q.dtype, T * (D // 2)), _operand(pos, "pos", torch.int32, B)
-    _bump_version(k_cache), _bump_version(v_cache)
-    dev = _same_device(q, k, v, cos, sin, pos, k_cache, v_cache)
-    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
-    _launch("asq_rope_quantize_qkv_at", dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[q.dtype], cos.data_ptr(), sin.data_ptr(), T, pos.data_ptr(),
-            q8.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), kvb, smax, float(q_scale), float(k_scale), float(v_scale), B, S, Hq, Hkv, D, _stream(q))
-    return q8, k_cache, v_cache
+    return _qkv_append("asq_rope_quantize_qkv_at", "cache", q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, k_cache, v_cache)
 
 
 def attn_decode_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, max_len=None):
@@ -824,22 +849,49 @@ def attn_decode_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, max_len=None
     h uses KV head h // r.  kv_len: int32 [B] on the device, sequence b attends keys 0 .. clamp(kv_len[b], 0, max_len) - 1 (None: max_len keys each); max_len: a
     bound on the lengths, Smax when absent.  out = sat_i8(rne(pv_alpha * (P . v))) with P = int8(rne(127 * softmax(qk_alpha * q . k^T))): bmm_i8_softmax_q8 followed by
     bmm_i8_kn(., torch.int8, pv_alpha), P never leaving the chip.  Shapes and strides are checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
-    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or q.dim() not in (3, 4) or (q.dim() == 4 and q.shape[1] != 1) or not q.is_contiguous():
-        raise ValueError(f"q must be a contiguous int8 [B, Hq, D] or [B, 1, Hq, D] tensor, got {getattr(q, 'dtype', type(q))} {list(getattr(q, 'shape', []))}")
-    B, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
-    smax, Hkv, kvb = _kv_caches(k_cache, v_cache, B, None, D)
+    return _attn_i8("asq_attn_decode_i8", False, False, q, k_cache, v_cache, None, kv_len, None, qk_alpha, pv_alpha, max_len)
+
+
+def _attn_i8(entry, multi, paged, q, k, v, table, kv_len, q_len, qk_alpha, pv_alpha, max_len):
+    """The four attention ops -> int8 of q's shape.  q: contiguous int8, one token per sequence ([B, Hq, D] or [B, 1, Hq, D]) or, multi, Sq tokens ([B, Sq, Hq, D]) with
+    q_len; k / v: the caches (_kv_caches) or, with a block table, the pools behind it (_kv_pools, _block_table); Hq = r * Hkv, r <= 16; max_len within the rows a sequence
+    can hold (those when absent), below 2^17, and 0 for a pool without pages; kv_len and q_len: _len_vec."""
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or not q.is_contiguous() or (q.dim() != 4 if multi else q.dim() not in (3, 4) or (q.dim() == 4 and q.shape[1] != 1)):
+        raise ValueError(f"q must be a contiguous int8 {'[B, Sq, Hq, D]' if multi else '[B, Hq, D] or [B, 1, Hq, D]'} tensor, got {getattr(q, 'dtype', type(q))} "
+                         f"{list(getattr(q, 'shape', []))}")
+    shape = q.shape
+    B, Hq, D = shape[0], shape[-2], shape[-1]
+    if multi:
+        _len_vec(q_len, "q_len", B)
+    if paged:
+        kn, vn = "k_pool", "v_pool"
+        num_pages, page_size, Hkv, pitch = _kv_pools(k, v, None, D)
+    else:
+        kn, vn, num_pages = "k_cache", "v_cache", 1
+        cap, Hkv, pitch = _kv_caches(k, v, B, None, D)
     if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
-        raise ValueError(f"q has {Hq} heads of {D}, the caches {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
-    max_len = smax if max_len is None else int(max_len)
-    if not 0 <= max_len <= smax or max_len >= 1 << 17:
-        raise ValueError(f"max_len {max_len} must be within the caches' {smax} rows and below 2^17")
-    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
-        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
-    _dev(q, "q"), _hip(k_cache, "k_cache"), _hip(v_cache, "v_cache"), _operand(kv_len, "kv_len", torch.int32, B, optional=True)
-    dev = _same_device(q, k_cache, v_cache, kv_len)
+        raise ValueError(f"q has {Hq} heads of {D}, the {'pools' if paged else 'caches'} {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
+    if paged:
+        tw, tp = _block_table(table, B)
+        cap, where = tw * page_size, (num_pages, page_size, pitch, tp)
+    else:
+        where = (pitch,)
+    max_len = cap if max_len is None else int(max_len)
+    if not 0 <= max_len <= cap or max_len >= 1 << 17 or (max_len > 0 and num_pages == 0):
+        room = f"the {tw} table entries x {page_size} rows of a sequence" if paged else f"the caches' {cap} rows"
+        raise ValueError(f"max_len {max_len} must be within {room}, below 2^17 and 0 for a pool without pages")
+    _len_vec(kv_len, "kv_len", B)
+    _dev(q, "q"), _hip(k, kn), _hip(v, vn)
+    if paged:
+        _hip(table, "block_table")
+    if kv_len is not None:
+        _dev(kv_len, "kv_len")
+    if q_len is not None:
+        _dev(q_len, "q_len")
+    dev = _same_device(q, k, v, table if paged else None, kv_len, q_len)
     out = torch.empty_like(q)
-    _launch("asq_attn_decode_i8", dev, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(kv_len), out.data_ptr(), B, Hq, Hkv, D, kvb, max_len,
-            float(qk_alpha), float(pv_alpha), _stream(q))
+    _launch(entry, dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), *((table.data_ptr(),) if paged else ()), _ptr(kv_len), *((_ptr(q_len),) if multi else ()), out.data_ptr(), B,
+            *((shape[1],) if multi else ()), Hq, Hkv, D, *where, max_len, float(qk_alpha), float(pv_alpha), _stream(q))
     return out
 
 
@@ -869,30 +921,7 @@ def rope_quantize_qkv_paged(q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, b
     int32 [B, T] on the device, row stride >= T.  max_len: rows per sequence, T * page_size when absent.
     A token with pos[b] < 0, pos[b] + s >= min(cos.shape[0], max_len) or a page id outside 0 .. num_pages - 1 writes nothing to the pools and gets a zero q8 row: the
     device checks, the host reads neither pos nor the table.  Every written byte equals rope_quantize_qkv_at writing the token into a contiguous cache."""
-    qld, kld, vld = _bshd_pitch(q, "q"), _bshd_pitch(k, "k"), _bshd_pitch(v, "v")
-    B, S, Hq, D = q.shape
-    Hkv = k.shape[2]
-    if k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or tuple(k.shape) != (B, S, Hkv, D):
-        raise ValueError(f"q {list(q.shape)} {q.dtype} must be [B, S, Hq, D], k {list(k.shape)} {k.dtype} and v {list(v.shape)} {v.dtype} [B, S, Hkv, D] of one dtype")
-    if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or D % 2 or cos.dim() != 2 or sin.shape != cos.shape or cos.shape[1] != D // 2:
-        raise ValueError(f"cos / sin must be [T, {D // 2}] tables, got {list(getattr(cos, 'shape', []))} and {list(getattr(sin, 'shape', []))}")
-    T = cos.shape[0]
-    num_pages, page_size, _, pitch = _kv_pools(k_pool, v_pool, Hkv, D)
-    tw, tp = _block_table(block_table, B)
-    max_len = tw * page_size if max_len is None else int(max_len)
-    if not 0 <= max_len <= tw * page_size:
-        raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence")
-    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or tuple(pos.shape) != (B,):
-        raise ValueError(f"pos must be an int32 [{B}] tensor, got {getattr(pos, 'dtype', type(pos))} {list(getattr(pos, 'shape', []))}")
-    _hip(q, "q"), _hip(k, "k"), _hip(v, "v"), _hip(k_pool, "k_pool"), _hip(v_pool, "v_pool"), _hip(block_table, "block_table")
-    _operand(cos, "cos", q.dtype, T * (D // 2)), _operand(sin, "sin", q.dtype, T * (D // 2)), _operand(pos, "pos", torch.int32, B)
-    _bump_version(k_pool), _bump_version(v_pool)
-    dev = _same_device(q, k, v, cos, sin, pos, block_table, k_pool, v_pool)
-    q8 = torch.empty((B, S, Hq, D), dtype=torch.int8, device=dev)
-    _launch("asq_rope_quantize_qkv_paged", dev, q.data_ptr(), k.data_ptr(), v.data_ptr(), qld, kld, vld, _DT[q.dtype], cos.data_ptr(), sin.data_ptr(), T, pos.data_ptr(),
-            block_table.data_ptr(), q8.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), num_pages, page_size, pitch, tp, max_len, float(q_scale), float(k_scale),
-            float(v_scale), B, S, Hq, Hkv, D, _stream(q))
-    return q8, k_pool, v_pool
+    return _qkv_append("asq_rope_quantize_qkv_paged", "pool", q, k, v, cos, sin, q_scale, k_scale, v_scale, pos, k_pool, v_pool, block_table, max_len)
 
 
 def attn_decode_i8_paged(q, k_pool, v_pool, block_table, kv_len, qk_alpha, pv_alpha, max_len=None):
@@ -902,33 +931,7 @@ def attn_decode_i8_paged(q, k_pool, v_pool, block_table, kv_len, qk_alpha, pv_al
     behind a sequence's last page are never read; sequences may share pages).  kv_len, qk_alpha, pv_alpha: attn_decode_i8's; max_len: a bound on the lengths, T * page_size
     when absent.  Every output byte equals attn_decode_i8 with the same max_len on a contiguous cache that holds each sequence's pages end to end.  Shapes and strides are
     checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
-    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or q.dim() not in (3, 4) or (q.dim() == 4 and q.shape[1] != 1) or not q.is_contiguous():
-        raise ValueError(f"q must be a contiguous int8 [B, Hq, D] or [B, 1, Hq, D] tensor, got {getattr(q, 'dtype', type(q))} {list(getattr(q, 'shape', []))}")
-    B, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
-    num_pages, page_size, Hkv, pitch = _kv_pools(k_pool, v_pool, None, D)
-    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
-        raise ValueError(f"q has {Hq} heads of {D}, the pools {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
-    tw, tp = _block_table(block_table, B)
-    max_len = tw * page_size if max_len is None else int(max_len)
-    if not 0 <= max_len <= tw * page_size or max_len >= 1 << 17 or (max_len > 0 and num_pages == 0):
-        raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence, below 2^17 and 0 for a pool without pages")
-    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
-        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
-    _dev(q, "q"), _hip(k_pool, "k_pool"), _hip(v_pool, "v_pool"), _hip(block_table, "block_table"), _operand(kv_len, "kv_len", torch.int32, B, optional=True)
-    dev = _same_device(q, k_pool, v_pool, block_table, kv_len)
-    out = torch.empty_like(q)
-    _launch("asq_attn_decode_i8_paged", dev, q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), _ptr(kv_len), out.data_ptr(), B, Hq, Hkv, D,
-            num_pages, page_size, pitch, tp, max_len, float(qk_alpha), float(pv_alpha), _stream(q))
-    return out
-
-
-def _extend_q(q, q_len):
-    """q and q_len of the extend ops: a contiguous int8 [B, Sq, Hq, D] tensor, q_len None or int32 [B] -> (B, Sq, Hq, D)"""
-    if not isinstance(q, torch.Tensor) or q.dtype != torch.int8 or q.dim() != 4 or not q.is_contiguous():
-        raise ValueError(f"q must be a contiguous int8 [B, Sq, Hq, D] tensor, got {getattr(q, 'dtype', type(q))} {list(getattr(q, 'shape', []))}")
-    if q_len is not None and (not isinstance(q_len, torch.Tensor) or q_len.dtype != torch.int32 or tuple(q_len.shape) != (q.shape[0],)):
-        raise ValueError(f"q_len must be None or an int32 [{q.shape[0]}] tensor, got {getattr(q_len, 'dtype', type(q_len))} {list(getattr(q_len, 'shape', []))}")
-    return tuple(q.shape)
+    return _attn_i8("asq_attn_decode_i8_paged", False, True, q, k_pool, v_pool, block_table, kv_len, None, qk_alpha, pv_alpha, max_len)
 
 
 def attn_extend_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, q_len=None, max_len=None):
@@ -938,45 +941,14 @@ def attn_extend_i8(q, k_cache, v_cache, kv_len, qk_alpha, pv_alpha, q_len=None, 
     at key position kv_len[b] - q_len[b] + s and sees the keys up to and including its own.  A padded token, and one that would see no key, gets a zero row.  Token (b, s)
     is attn_decode_i8's arithmetic over its own keys; min(Sq, 16 // r) tokens share a workgroup and one read of K and V.  Shapes and strides are checked first (ValueError),
     then the devices (RuntimeError: no CPU fallback)."""
-    B, Sq, Hq, D = _extend_q(q, q_len)
-    smax, Hkv, kvb = _kv_caches(k_cache, v_cache, B, None, D)
-    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
-        raise ValueError(f"q has {Hq} heads of {D}, the caches {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
-    max_len = smax if max_len is None else int(max_len)
-    if not 0 <= max_len <= smax or max_len >= 1 << 17:
-        raise ValueError(f"max_len {max_len} must be within the caches' {smax} rows and below 2^17")
-    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
-        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
-    _dev(q, "q"), _hip(k_cache, "k_cache"), _hip(v_cache, "v_cache")
-    _operand(kv_len, "kv_len", torch.int32, B, optional=True), _operand(q_len, "q_len", torch.int32, B, optional=True)
-    dev = _same_device(q, k_cache, v_cache, kv_len, q_len)
-    out = torch.empty_like(q)
-    _launch("asq_attn_extend_i8", dev, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(kv_len), _ptr(q_len), out.data_ptr(), B, Sq, Hq, Hkv, D, kvb, max_len,
-            float(qk_alpha), float(pv_alpha), _stream(q))
-    return out
+    return _attn_i8("asq_attn_extend_i8", True, False, q, k_cache, v_cache, None, kv_len, q_len, qk_alpha, pv_alpha, max_len)
 
 
 def attn_extend_i8_paged(q, k_pool, v_pool, block_table, kv_len, qk_alpha, pv_alpha, q_len=None, max_len=None):
     """attn_extend_i8 on paged caches in ONE launch (asq_attn_extend_i8_paged): q int8 [B, Sq, Hq, D], contiguous -> int8 of q's shape.  k_pool, v_pool, block_table,
     kv_len, max_len: attn_decode_i8_paged's; q_len and the per-token rule: attn_extend_i8's.  Every output byte equals attn_extend_i8 with the same max_len on a contiguous
     cache that holds each sequence's pages end to end.  Shapes and strides are checked first (ValueError), then the devices (RuntimeError: no CPU fallback)."""
-    B, Sq, Hq, D = _extend_q(q, q_len)
-    num_pages, page_size, Hkv, pitch = _kv_pools(k_pool, v_pool, None, D)
-    if Hkv == 0 or Hq % Hkv or Hq // Hkv > 16 or D % 16 or D > 256:
-        raise ValueError(f"q has {Hq} heads of {D}, the pools {Hkv}: Hq must be r * Hkv with 1 <= r <= 16 and D a multiple of 16 up to 256")
-    tw, tp = _block_table(block_table, B)
-    max_len = tw * page_size if max_len is None else int(max_len)
-    if not 0 <= max_len <= tw * page_size or max_len >= 1 << 17 or (max_len > 0 and num_pages == 0):
-        raise ValueError(f"max_len {max_len} must be within the {tw} table entries x {page_size} rows of a sequence, below 2^17 and 0 for a pool without pages")
-    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
-        raise ValueError(f"kv_len must be None or an int32 [{B}] tensor, got {getattr(kv_len, 'dtype', type(kv_len))} {list(getattr(kv_len, 'shape', []))}")
-    _dev(q, "q"), _hip(k_pool, "k_pool"), _hip(v_pool, "v_pool"), _hip(block_table, "block_table")
-    _operand(kv_len, "kv_len", torch.int32, B, optional=True), _operand(q_len, "q_len", torch.int32, B, optional=True)
-    dev = _same_device(q, k_pool, v_pool, block_table, kv_len, q_len)
-    out = torch.empty_like(q)
-    _launch("asq_attn_extend_i8_paged", dev, q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), _ptr(kv_len), _ptr(q_len), out.data_ptr(), B, Sq,
-            Hq, Hkv, D, num_pages, page_size, pitch, tp, max_len, float(qk_alpha), float(pv_alpha), _stream(q))
-    return out
+    return _attn_i8("asq_attn_extend_i8_paged", True, True, q, k_pool, v_pool, block_table, kv_len, q_len, qk_alpha, pv_alpha, max_len)
 
 
 def silu_mul_quantize_fp8(gate, up, fast=None):

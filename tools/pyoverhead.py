@@ -1,4 +1,4 @@
-"""Host time per call at decode sizes: the module call, the bare C-ABI call under it, and the general-checker ops.
+"""Host time per call at decode sizes: the module call, the bare C-ABI call under it, the general-checker ops and the seven ops of the int8 KV-cache family.
     python tools/pyoverhead.py [--root CHECKOUT] [--brief]
 --root: measure the package of another checkout (an A/B of two versions of the Python layer); --brief: the timed loops only."""
 import argparse, os, sys, time
@@ -55,10 +55,28 @@ print('two torch.empty us', (t1 - t0) / 2000 * 1e6)
 xq = torch.randint(-128, 128, (M, K), dtype=torch.int8, device=dev)
 qa = torch.randint(-128, 128, (32, 1, 128), dtype=torch.int8, device=dev)       # one decode step of 32 heads against 1024 cached keys
 kb = torch.randint(-128, 128, (32, 1024, 128), dtype=torch.int8, device=dev)
+# the int8 KV-cache family at a decode step: 32 sequences, 32 query heads over 8 KV heads of 128, 1024 cached keys each (the extend forms: 4 tokens per sequence);
+# paged: 64 pages of 16 rows per sequence
+B_, HQ, HKV, D_, NK, SQ, PS = 32, 32, 8, 128, 1024, 4, 16
+f16 = lambda *s: torch.randn(s, dtype=torch.float16, device=dev)  # noqa: E731
+i8 = lambda *s: torch.randint(-128, 128, s, dtype=torch.int8, device=dev)  # noqa: E731
+q1, k1, v1, cos, sin = f16(B_, 1, HQ, D_), f16(B_, 1, HKV, D_), f16(B_, 1, HKV, D_), f16(NK, D_ // 2), f16(NK, D_ // 2)
+kc, vc, kp, vp = i8(B_, NK, HKV, D_), i8(B_, NK, HKV, D_), i8(B_ * NK // PS, PS, HKV, D_), i8(B_ * NK // PS, PS, HKV, D_)
+ko, vo = kc[:, NK - 1:], vc[:, NK - 1:]
+tab = torch.arange(B_ * NK // PS, dtype=torch.int32, device=dev).view(B_, NK // PS)
+pos, n, ql = (torch.full((B_,), v_, dtype=torch.int32, device=dev) for v_ in (NK - 1, NK, SQ))
+q8d, q8e = i8(B_, 1, HQ, D_), i8(B_, SQ, HQ, D_)
 for name, fn in (("ops.linear_w8a8_forward", lambda: ops.linear_w8a8_forward(x, m.weight, "per-tensor-round", 1.0, 1.0)),
                  ("ops.linear_w8a8", lambda: ops.linear_w8a8(xq, m.weight, torch.float16, 1e-3)),
                  ("ops.quantize_act", lambda: ops.quantize_act(x, "per-tensor-round")),
-                 ("ops.bmm_i8", lambda: ops.bmm_i8(qa, kb, torch.float32, 0.1))):
+                 ("ops.bmm_i8", lambda: ops.bmm_i8(qa, kb, torch.float32, 0.1)),
+                 ("ops.rope_quantize_qkv", lambda: ops.rope_quantize_qkv(q1, k1, v1, cos, sin, 0.05, 0.05, 0.05, pos=NK - 1, k_out=ko, v_out=vo)),
+                 ("ops.rope_quantize_qkv_at", lambda: ops.rope_quantize_qkv_at(q1, k1, v1, cos, sin, 0.05, 0.05, 0.05, pos, kc, vc)),
+                 ("ops.rope_quantize_qkv_paged", lambda: ops.rope_quantize_qkv_paged(q1, k1, v1, cos, sin, 0.05, 0.05, 0.05, pos, tab, kp, vp)),
+                 ("ops.attn_decode_i8", lambda: ops.attn_decode_i8(q8d, kc, vc, n, 0.01, 0.02)),
+                 ("ops.attn_decode_i8_paged", lambda: ops.attn_decode_i8_paged(q8d, kp, vp, tab, n, 0.01, 0.02)),
+                 ("ops.attn_extend_i8", lambda: ops.attn_extend_i8(q8e, kc, vc, n, 0.01, 0.02, q_len=ql)),
+                 ("ops.attn_extend_i8_paged", lambda: ops.attn_extend_i8_paged(q8e, kp, vp, tab, n, 0.01, 0.02, q_len=ql))):
     for _ in range(20): fn()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
