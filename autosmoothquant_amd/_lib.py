@@ -1,5 +1,5 @@
-"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h, include/asq_hip_decode.h, include/asq_hip_paged.h and
-include/asq_hip_extend.h)."""
+"""ctypes loader for libasq_hip.so (the C-ABI declared in include/asq_hip.h, include/asq_hip_attn.h, include/asq_hip_decode.h, include/asq_hip_paged.h,
+include/asq_hip_extend.h and include/asq_hip_moe.h)."""
 import ctypes
 import os
 import threading
@@ -130,6 +130,15 @@ EXTEND_SIGNATURES = {
     "asq_attn_extend_i8_paged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
 }
 
+# include/asq_hip_moe.h: the routing around the grouped expert launches (top-k route + stable sort, dispatching quantiser, gather combine), a sixth table:
+# EXTEND_SIGNATURES is tied to its guard-band file; probed by presence, ASQ_VERSION stays
+MOE_SIGNATURES = {
+    "asq_moe_route_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "asq_moe_route": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "asq_moe_dispatch_quantize": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp]),
+    "asq_moe_combine": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+}
+
 
 def lib():
     """Load libasq_hip.so once.  Fails loudly: there is no fallback implementation."""
@@ -149,7 +158,7 @@ def lib():
                 import torch  # noqa: F401
                 h = ctypes.CDLL(LIB_PATH)
                 for name, (res, args) in list(SIGNATURES.items()) + list(ATTN_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()) + list(PAGED_SIGNATURES.items()) + \
-                        list(EXTEND_SIGNATURES.items()):
+                        list(EXTEND_SIGNATURES.items()) + list(MOE_SIGNATURES.items()):
                     fn = getattr(h, name)  # AttributeError if the .so lacks a declared symbol
                     fn.restype, fn.argtypes = res, args
                 if h.asq_version() != ASQ_VERSION:   # a stale build: argument lists and the workspace contract may differ

@@ -190,6 +190,19 @@ template <int DT> __device__ __forceinline__ void vec_unpack(const v4i &v, float
     }
 }
 
+// the reverse: floats rounded to DT (one RNE each) as one 16-byte vector
+template <int DT> __device__ __forceinline__ v4i vec_pack(const float (&f)[ElemT<DT>::VEC])
+{
+    if constexpr (DT == ASQ_F32) {
+        return (v4i){__float_as_int(f[0]), __float_as_int(f[1]), __float_as_int(f[2]), __float_as_int(f[3])};
+    } else {
+        v4i v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = (int)((uint32_t)ElemT<DT>::store(f[2 * i]) | ((uint32_t)ElemT<DT>::store(f[2 * i + 1]) << 16));
+        return v;
+    }
+}
+
 template <int DT> struct AbsMax {  // running |x| maximum of raw DT vectors
     uint32_t acc = 0;              // fp32: |bits|;  16-bit types: two packed 15-bit patterns
     __device__ __forceinline__ void add(const v4i &v)

@@ -172,64 +172,7 @@ template <int DT> int quantize_dt(const void *x, int mode, float quant_scale, in
 //     weights      cw = min(CW, 127 - max_k w)                                                     (CW = 64)
 // (profiles/r4_operand_offsets.md: what the matrix cores sustain for which offsets; oracle/offsets.py restates both rules.)
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(v2us, a), __builtin_bit_cast(v2us, b)));
-}
-// running max / min / sum of packed int8 words, carried on the bytes biased by +128 (0..255) as pairs of 16-bit lanes: no unpacking
-struct RowStats {
-    uint32_t mx = 0, mn = 0x00FF00FFu, sum = 0;   // (sum: two 16-bit partial sums of biased bytes -- at most 2 * 160 words * 255 per thread)
-    int n = 0;                                    // bytes added
-    __device__ __forceinline__ void add(uint32_t packed)
-    {
-        const uint32_t u = packed ^ 0x80808080u, a = u & 0x00FF00FFu, b = (u >> 8) & 0x00FF00FFu;
-        mx = pk_max_u16(mx, pk_max_u16(a, b));
-        mn = pk_min_u16(mn, pk_min_u16(a, b));
-        sum += a + b;
-        n += 4;
-    }
-    // branch-free form for a lane whose vector may be a DUPLICATE of a valid one (max / min do not care; sum and count must skip it)
-    __device__ __forceinline__ void add(uint32_t packed, bool valid)
-    {
-        const uint32_t u = packed ^ 0x80808080u, a = u & 0x00FF00FFu, b = (u >> 8) & 0x00FF00FFu;
-        mx = pk_max_u16(mx, pk_max_u16(a, b));
-        mn = pk_min_u16(mn, pk_min_u16(a, b));
-        sum += valid ? a + b : 0u;
-        n += valid ? 4 : 0;
-    }
-};
-// block-wide (256 threads) max / min / sum of the quantised row; red: 12 ints of shared memory
-__device__ __forceinline__ void block_row_stats(const RowStats &st, int *red, int &rmax, int &rmin, int &rsum)
-{
-    int mx = (int)umax32(st.mx & 0xFFFFu, st.mx >> 16) - 128, mn = (int)(((st.mn & 0xFFFFu) < (st.mn >> 16)) ? (st.mn & 0xFFFFu) : (st.mn >> 16)) - 128;
-    int sm = (int)((st.sum & 0xFFFFu) + (st.sum >> 16)) - 128 * st.n;
-    if (st.n == 0) { mx = -128; mn = 127; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int omx = __shfl_xor(mx, off, 64), omn = __shfl_xor(mn, off, 64);
-        mx = mx > omx ? mx : omx;
-        mn = mn < omn ? mn : omn;
-        sm += __shfl_xor(sm, off, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();   // (red may still be read by a previous reduction)
-    if ((threadIdx.x & 63) == 0) { red[wave] = mx; red[4 + wave] = mn; red[8 + wave] = sm; }
-    __syncthreads();
-    const int a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
-    const int c = red[4] < red[5] ? red[4] : red[5], d = red[6] < red[7] ? red[6] : red[7];
-    rmax = a > b ? a : b;
-    rmin = c < d ? c : d;
-    rsum = (red[8] + red[9]) + (red[10] + red[11]);
-}
-__device__ __forceinline__ int pick_row_offset(int rmax, int rmin, int C)
-{
-    return rmax <= 127 - C ? C : (rmin >= -128 + C ? -C : 0);
-}
-// four packed int8 + the same small constant each, no carries between the bytes (the caller guarantees every sum stays in [-128, 127])
-__device__ __forceinline__ uint32_t pk_add_i8(uint32_t a, uint32_t c4)
-{
-    return ((a & 0x7F7F7F7Fu) + (c4 & 0x7F7F7F7Fu)) ^ ((a ^ c4) & 0x80808080u);
-}
+// (RowStats, block_row_stats, pick_row_offset and pk_add_i8 -- the row statistics and the offset rule -- live in asq_quant_core.h: asq_moe.hip states them too)
 
 // any of the three activation quantisers with row offsets: one 256-thread block per row, the row in registers (as quant_per_token_cached), the
 // quantised row kept PACKED in registers between the statistics and the store.  K % VEC == 0, K <= 256 * VEC * NV, 16-byte aligned rows.
@@ -530,18 +473,6 @@ __device__ __forceinline__ float block_sum_256(float v, float *red)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-template <int DT> __device__ __forceinline__ v4i vec_pack(const float (&f)[ElemT<DT>::VEC])
-{
-    if constexpr (DT == ASQ_F32) {
-        return (v4i){__float_as_int(f[0]), __float_as_int(f[1]), __float_as_int(f[2]), __float_as_int(f[3])};
-    } else {
-        v4i v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (int)((uint32_t)ElemT<DT>::store(f[2 * i]) | ((uint32_t)ElemT<DT>::store(f[2 * i + 1]) << 16));
-        return v;
-    }
 }
 
 // ADD = 1: the residual-add form (the reference's dq_add_layernorm_q, csrc/kernels/fused.cu:5-25, with a floating `x`
@@ -929,6 +860,8 @@ int launch_silu_mul_quant(const void *g, const void *u, float qs, int8_t *xq, fl
 }
 }  // namespace asq
 using namespace asq;
+
+int asq_offset_cx() { return offset_cx(); }   // (asq_quant_core.h: the same C for asq_moe.hip's dispatching quantiser)
 
 extern "C" int asq_quantize_act(const void *x, int x_dtype, int mode, float quant_scale, int8_t *xq, float *s_row,
                                 int64_t M, int64_t K, void *stream)

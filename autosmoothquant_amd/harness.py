@@ -837,56 +837,81 @@ class MixtralLayer(LlamaLayer):
                     return False
         return True
 
+    fused_route = False   # opt-in: route, dispatch + quantise and combine as the three device steps of include/asq_hip_moe.h (see moe())
+
+    def _grouped_ok(self, x2):
+        """the grouped launches run on the tiled kernel: stacks, per-token w2, a HIP tensor, K % 128 == 0 for both projections"""
+        return (hasattr(self, "_w1_stack") and self.experts[0].w2.act_quant == "per-token" and x2.is_cuda
+                and x2.shape[-1] % 128 == 0 and self._w2_stack.shape[-1] % 128 == 0)
+
+    def _grouped_experts(self, R, H, dtype, offs, quantize):
+        """Every expert projection of the R routed rows as one grouped launch each -> y [R, H] in sorted-row order.  quantize(mode, quant_scale, offsets) ->
+        (xq, s_row, row_off or None) of the routed rows: the gather + quantiser of moe(), or the dispatching quantiser of its fused_route form."""
+        from . import ops
+        ex = self.experts
+        mode, qs = ex[0].w1._input_mode()
+        if getattr(self, "offsets", True) and ops.grouped_offsets_supported(R, self._w1_stack.shape[1], H, dtype) and ops.grouped_offsets_supported(R, H, self._w2_stack.shape[-1], dtype):
+            # offset operand images (include/asq_hip.h): same products, less matrix-core energy; the stacks' images are built once and follow the stacks
+            i1, i3, i2 = (self._stack_image(n) for n in ("w1", "w3", "w2"))
+        else:
+            i1 = i3 = i2 = None
+        F2 = self._w1_stack.shape[1]
+        gate_up = (getattr(self, "fuse_gate_up", False) and mode != "per-token" and ops.grouped_gate_up_supported(R, F2, H, dtype))
+        if gate_up:
+            # opt-in (round 5): w1 || w3 of all experts as ONE grouped launch whose epilogue writes SiLU(w1 x) * (w3 x) -- the fused-SiLU arithmetic (+-1 int8 of torch's
+            # silu at rounding boundaries, like ops.silu_mul_quantize), which is why the reference composition below stays the default
+            w13, img13 = self._w13_operand(i1 is not None and i2 is not None)
+            gate_up = w13 is not None
+        if gate_up:
+            if img13 is not None and i2 is not None:
+                xq, _, ro = quantize(mode, qs, True)
+                a = ops.linear_w8a8_grouped_gate_up(xq, img13[0], offs, self._w1_scale, self._w3_scale, dtype, getattr(self, "fast_silu", None), ro, img13[1])
+                aq, arow, ao = ops.quantize_act_off(a, "per-token")
+                return ops.linear_w8a8_grouped_off(aq, i2[0], ao, i2[1], offs, self._w2_scale, dtype, arow)
+            xq, _, _ = quantize(mode, qs, False)
+            a = ops.linear_w8a8_grouped_gate_up(xq, w13, offs, self._w1_scale, self._w3_scale, dtype, getattr(self, "fast_silu", None))
+            aq, arow = ops.quantize_act(a, "per-token")
+            return ops.linear_w8a8_grouped(aq, self._w2_stack, offs, self._w2_scale, dtype, arow)
+        if i1 is not None and i3 is not None and i2 is not None:
+            xq, srow, ro = quantize(mode, qs, True)
+            h1 = ops.linear_w8a8_grouped_off(xq, i1[0], ro, i1[1], offs, self._w1_scale, dtype, srow)
+            h3 = ops.linear_w8a8_grouped_off(xq, i3[0], ro, i3[1], offs, self._w3_scale, dtype, srow)
+            aq, arow, ao = ops.quantize_act_off(F.silu(h1) * h3, "per-token")
+            return ops.linear_w8a8_grouped_off(aq, i2[0], ao, i2[1], offs, self._w2_scale, dtype, arow)
+        xq, srow, _ = quantize(mode, qs, False)
+        h1 = ops.linear_w8a8_grouped(xq, self._w1_stack, offs, self._w1_scale, dtype, srow)
+        h3 = ops.linear_w8a8_grouped(xq, self._w3_stack, offs, self._w3_scale, dtype, srow)
+        aq, arow = ops.quantize_act(F.silu(h1) * h3, "per-token")
+        return ops.linear_w8a8_grouped(aq, self._w2_stack, offs, self._w2_scale, dtype, arow)
+
     def moe(self, x):
+        """The sparse MoE block.  With the class attribute `fused_route` set and the grouped path taken, the glue around the grouped launches is three device steps
+        (ops.moe_route on the router's logits, ops.moe_dispatch_quantize, ops.moe_combine) instead of softmax / topk / sort / bincount / cumsum, the gather + quantiser
+        and y * wts + index_add_: the same sorted rows, offsets and GEMM operands, hence the same expert outputs; the combine rounds ONCE (fp32 accumulation in slot
+        order) where y * wts + index_add_ round up to three times, so the last place of the result can differ -- which is why it is an opt-in."""
         B, S, H = x.shape
         x2 = x.reshape(-1, H)
+        if self.fused_route and self._grouped_ok(x2):
+            from . import ops
+            if not self._stacks_current():
+                self.stack_experts()
+            x2 = x2.contiguous()
+            _, wts, offs, _, inv = ops.moe_route(self.gate(x2), self.top_k, x2.dtype)
+            y = self._grouped_experts(inv.numel(), H, x.dtype, offs, lambda mode, qs, off: ops.moe_dispatch_quantize(x2, inv, mode, qs, offsets=off))
+            return ops.moe_combine(y, wts, inv).view(B, S, H)
         tok, wts, counts = self.route(x2)
         xs = x2[tok]
         ex = self.experts
-        grouped = (hasattr(self, "_w1_stack") and ex[0].w2.act_quant == "per-token" and xs.is_cuda
-                   and H % 128 == 0 and self._w2_stack.shape[-1] % 128 == 0)   # (the grouped launch runs on the tiled kernel: K % 128 == 0)
+        grouped = self._grouped_ok(xs)
         if grouped and not self._stacks_current():   # a buffer was re-homed or a scale rewritten since stack_experts(): rebuild from the per-expert modules
             self.stack_experts()
         if grouped:
             from . import ops
             offs = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32)
-            mode, qs = ex[0].w1._input_mode()
-            R = xs.shape[0]
-            if getattr(self, "offsets", True) and ops.grouped_offsets_supported(R, self._w1_stack.shape[1], H, x.dtype) and ops.grouped_offsets_supported(R, H, self._w2_stack.shape[-1], x.dtype):
-                # offset operand images (include/asq_hip.h): same products, less matrix-core energy; the stacks' images are built once and follow the stacks
-                i1, i3, i2 = (self._stack_image(n) for n in ("w1", "w3", "w2"))
-            else:
-                i1 = i3 = i2 = None
-            F2 = self._w1_stack.shape[1]
-            gate_up = (getattr(self, "fuse_gate_up", False) and mode != "per-token" and ops.grouped_gate_up_supported(R, F2, H, x.dtype))
-            if gate_up:
-                # opt-in (round 5): w1 || w3 of all experts as ONE grouped launch whose epilogue writes SiLU(w1 x) * (w3 x) -- the fused-SiLU arithmetic (+-1 int8 of torch's
-                # silu at rounding boundaries, like ops.silu_mul_quantize), which is why the reference composition below stays the default
-                w13, img13 = self._w13_operand(i1 is not None and i2 is not None)
-                gate_up = w13 is not None
-            if gate_up:
-                if img13 is not None and i2 is not None:
-                    xq, _, ro = ops.quantize_act_off(xs.contiguous(), mode, qs)
-                    a = ops.linear_w8a8_grouped_gate_up(xq, img13[0], offs, self._w1_scale, self._w3_scale, x.dtype, getattr(self, "fast_silu", None), ro, img13[1])
-                    aq, arow, ao = ops.quantize_act_off(a, "per-token")
-                    y = ops.linear_w8a8_grouped_off(aq, i2[0], ao, i2[1], offs, self._w2_scale, x.dtype, arow)
-                else:
-                    xq, _ = ops.quantize_act(xs.contiguous(), mode, qs)
-                    a = ops.linear_w8a8_grouped_gate_up(xq, w13, offs, self._w1_scale, self._w3_scale, x.dtype, getattr(self, "fast_silu", None))
-                    aq, arow = ops.quantize_act(a, "per-token")
-                    y = ops.linear_w8a8_grouped(aq, self._w2_stack, offs, self._w2_scale, x.dtype, arow)
-            elif i1 is not None and i3 is not None and i2 is not None:
-                xq, srow, ro = ops.quantize_act_off(xs.contiguous(), mode, qs)
-                h1 = ops.linear_w8a8_grouped_off(xq, i1[0], ro, i1[1], offs, self._w1_scale, x.dtype, srow)
-                h3 = ops.linear_w8a8_grouped_off(xq, i3[0], ro, i3[1], offs, self._w3_scale, x.dtype, srow)
-                aq, arow, ao = ops.quantize_act_off(F.silu(h1) * h3, "per-token")
-                y = ops.linear_w8a8_grouped_off(aq, i2[0], ao, i2[1], offs, self._w2_scale, x.dtype, arow)
-            else:
-                xq, srow = ops.quantize_act(xs.contiguous(), mode, qs)
-                h1 = ops.linear_w8a8_grouped(xq, self._w1_stack, offs, self._w1_scale, x.dtype, srow)
-                h3 = ops.linear_w8a8_grouped(xq, self._w3_stack, offs, self._w3_scale, x.dtype, srow)
-                aq, arow = ops.quantize_act(F.silu(h1) * h3, "per-token")
-                y = ops.linear_w8a8_grouped(aq, self._w2_stack, offs, self._w2_scale, x.dtype, arow)
+
+            def quantize(mode, qs, off):
+                return ops.quantize_act_off(xs.contiguous(), mode, qs) if off else (*ops.quantize_act(xs.contiguous(), mode, qs), None)
+            y = self._grouped_experts(xs.shape[0], H, x.dtype, offs, quantize)
         else:   # the reference's loop (also the float layer's path)
             y, o = torch.empty_like(xs), 0
             for e, c in zip(ex, counts.tolist()):

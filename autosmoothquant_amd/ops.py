@@ -1258,3 +1258,50 @@ def linear_fp8_grouped(xq, a_scale, w, w_scale_group, group_offsets, out_dtype, 
     _launch("asq_linear_fp8_grouped", _same_device(xq, w, group_offsets, w_scale_group, a_scale, bias), xq.data_ptr(), w.data_ptr(), out.data_ptr(), _DT[out_dtype],
             group_offsets.data_ptr(), G, M, N, K, a_scale.data_ptr(), w_scale_group.data_ptr(), _ptr(bias), _stream(xq))
     return out
+
+
+# ---- include/asq_hip_moe.h: the routing around the grouped expert launches ------------------------------------------------------------------------------
+def moe_route(logits, top_k, w_dtype):
+    """Router logits [T, E] f32/f16/bf16 -> (sel int32 [T, k] best first, wts f32 [T, k] holding values of w_dtype, group_offsets int32 [E + 1],
+    tok int32 [T * k] the token of each sorted row, inv int32 [T, k] the sorted row of pair (t, j)): include/asq_hip_moe.h's rule, at most two launches,
+    nothing read back to the host.  1 <= E <= 64, 1 <= top_k <= min(E, 8)."""
+    T, E = _float_rows(logits)
+    if w_dtype not in _DT:
+        raise ValueError(f"w_dtype must be float32, float16 or bfloat16, got {w_dtype}")
+    top_k, dev = int(top_k), logits.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    sel, inv, tok, offs = torch.empty((T, top_k), **i32), torch.empty((T, top_k), **i32), torch.empty((T * max(top_k, 0),), **i32), torch.empty((E + 1,), **i32)
+    wts = torch.empty((T, top_k), dtype=torch.float32, device=dev)
+    n = L.lib().asq_moe_route_workspace_bytes(T, E, top_k)
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev) if n else None
+    _launch("asq_moe_route", dev, logits.data_ptr(), _DT[logits.dtype], T, E, top_k, _DT[w_dtype], sel.data_ptr(), wts.data_ptr(), offs.data_ptr(), tok.data_ptr(),
+            inv.data_ptr(), _ptr(ws), n, _stream(logits))
+    return sel, wts, offs, tok, inv
+
+
+def moe_dispatch_quantize(x, inv, mode, quant_scale=1.0, offsets=False):
+    """quantize_act (offsets: quantize_act_off) of the gathered rows x[tok] without the gather: x [T, K] is read and quantised once per token and written to the
+    rows inv [T, k] names -> (xq int8 [T * k, K], s_row f32 [T * k] or None, row_off int32 [T * k, 2] or None).  K % 16 == 0, K <= 16384 (f32: 8192)."""
+    T, K = _float_rows(x)
+    _operand(inv, "inv", torch.int32)
+    if inv.dim() != 2 or inv.shape[0] != T:
+        raise ValueError(f"inv must be int32 [T, top_k] with T = {T}, got {list(inv.shape)}")
+    k = inv.shape[1]
+    xq, s_row, row_off = _rows_out(T * k, K, x.device, mode == "per-token", offsets)
+    _launch("asq_moe_dispatch_quantize", _same_device(x, inv), x.data_ptr(), _DT[x.dtype], inv.data_ptr(), T, k, K, _ACT[mode], float(quant_scale), xq.data_ptr(),
+            _ptr(s_row), _ptr(row_off), _stream(x))
+    return xq, s_row, row_off
+
+
+def moe_combine(y, wts, inv):
+    """out [T, H] = dt(sum_j f32(y[inv[t, j]]) * wts[t, j]), fp32 multiply then fp32 add in slot order, one rounding: y [T * k, H] f32/f16/bf16 (the experts' output
+    in sorted-row order), wts f32 [T, k], inv int32 [T, k].  A gather: every row of out is written, nothing is zero-filled, no atomics.  H % 8 == 0 (f32: 4)."""
+    R, H = _float_rows(y)
+    _operand(inv, "inv", torch.int32)
+    if inv.dim() != 2 or inv.numel() != R:
+        raise ValueError(f"inv must be int32 [T, top_k] with T * top_k = {R} rows of y, got {list(inv.shape)}")
+    T, k = inv.shape
+    _operand(wts, "wts", torch.float32, shape=(T, k))
+    out = torch.empty((T, H), dtype=y.dtype, device=y.device)
+    _launch("asq_moe_combine", _same_device(y, wts, inv), y.data_ptr(), _DT[y.dtype], wts.data_ptr(), inv.data_ptr(), out.data_ptr(), T, k, H, _stream(y))
+    return out
